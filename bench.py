@@ -12,7 +12,11 @@ TrustRegion accept/reject) over the whole scene.  Inputs are resident in HBM bef
     python bench.py --path tracks|passes|mapper   track establishment, the between-round passes, the config-5 mapper
 
 
-Rank 0 prints one JSON line.  The CPU baseline (rank 0, N=1 only) is the build's C/OpenMP restatement of the same LM
+A plain run sets up, warms up, times the K steps and prints the result line (rank 0, one JSON line).  --dump-outputs DIR
+also writes what the last timed step returned as DIR/<name>.npy.  --full adds everything that takes runs of its own:
+the instrumented replay (phase split), per-kernel and roofline timings, the end-to-end Solve split, the CPU baseline.
+
+The CPU baseline (--full, rank 0, N=1 only) is the build's C/OpenMP restatement of the same LM
 (oracle/ba_oracle.c; the reference has no CPU BA) run to convergence on the same scene.
 """
 import argparse
@@ -79,6 +83,30 @@ def algorithmic_bytes(kernel, C, P, N, D, nnzb, extra=None):
                 + N * w_record_doubles(D) * 8  # W records written
                 + P * 9 * 8)           # V (6) + g_p (3) written
     raise ValueError(kernel)
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20  # --dump-outputs: ceiling on the bytes written, all arrays together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write what the timed path's last step returned as DIR/<name>.npy (float64 arrays as they are,
+    float32 as they are, anything else as float64, which holds every int32 exactly).  An array larger than its share of
+    DUMP_BUDGET_BYTES is cut to a fixed sample of its rows (axis 0; the same sorted, seeded row indices in every run
+    of the same shape), so two builds given the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.atleast_1d(np.asarray(a))
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            keep = max(1, share // max(1, a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(prob, max_steps, min_seconds=10.0, max_runs=8, cluster_size=24, precond=2):
@@ -182,21 +210,11 @@ def run_gp(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss, rmse = eng.cost(*par)
-    tl = args.precond >= 1
-    us_cg = eng.debug_time_kernel(3 if tl else 0, 100)
-    us_schur = eng.debug_time_kernel(1, 5)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cams": par[0], "points": par[1], "scales": par[2], "loss": losses[-1:]})
     C, P, N, D = prob.n_cams, prob.n_points, prob.n_obs, 3
-    Pl = shards[rank][1] - shards[rank][0]
-    Nl = int(np.sum((prob.pt_idx >= shards[rank][0]) & (prob.pt_idx < shards[rank][1])))
     nnzb = eng.nnzb()
     trials = sum(s["trials"] for s in stats)
-    cg_launches = sum(s["cg_launches"] for s in stats)
-    kcg = "k_tl_pspmv" if tl else "k_cg_iter"
-    kern = {kcg: (us_cg * cg_launches, cg_launches, us_cg, algorithmic_bytes(kcg, C, Pl, Nl, D, nnzb)),
-            "k_schur": (us_schur * trials, trials, us_schur, algorithmic_bytes("k_schur", C, Pl, Nl, D, nnzb))}
-    name = max(kern, key=lambda k: kern[k][0])
-    _, launches, avg_us, nbytes = kern[name]
-    achieved = nbytes / (avg_us * 1e-6) / 1e9 if avg_us > 0 else 0.0
     out = {
         "metric": "LM-GP iterations/sec (global positioning, TorchGP.Optimize)",
         "value": round(args.steps / dt, 4), "unit": "LM it/s", "n_gpus": world, "steps": args.steps,
@@ -209,13 +227,27 @@ def run_gp(args):
                    "parallelism": f"track-shard x{world}" if world > 1 else "single GPU"},
         "final_loss": final_loss, "final_rmse": rmse, "loss_history": [round(x, 6) for x in losses],
         "pcg_iters": [s["pcg_iters"] for s in stats], "trials": trials,
-        "kernel_us": {kcg: round(us_cg, 3), "k_schur": round(us_schur, 2)},
-        "roofline": {"kernel": name, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                     "avg_launch_us": round(avg_us, 3), "algorithmic_bytes_per_launch": int(nbytes),
-                     "launches_per_run": int(launches)},
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full:
+        # per-kernel device times (runs of their own) and the dominant kernel's roofline entry
+        tl = args.precond >= 1
+        us_cg = eng.debug_time_kernel(3 if tl else 0, 100)
+        us_schur = eng.debug_time_kernel(1, 5)
+        Pl = shards[rank][1] - shards[rank][0]
+        Nl = int(np.sum((prob.pt_idx >= shards[rank][0]) & (prob.pt_idx < shards[rank][1])))
+        cg_launches = sum(s["cg_launches"] for s in stats)
+        kcg = "k_tl_pspmv" if tl else "k_cg_iter"
+        kern = {kcg: (us_cg * cg_launches, cg_launches, us_cg, algorithmic_bytes(kcg, C, Pl, Nl, D, nnzb)),
+                "k_schur": (us_schur * trials, trials, us_schur, algorithmic_bytes("k_schur", C, Pl, Nl, D, nnzb))}
+        name = max(kern, key=lambda k: kern[k][0])
+        _, launches, avg_us, nbytes = kern[name]
+        achieved = nbytes / (avg_us * 1e-6) / 1e9 if avg_us > 0 else 0.0
+        out["kernel_us"] = {kcg: round(us_cg, 3), "k_schur": round(us_schur, 2)}
+        out["roofline"] = {"kernel": name, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                           "avg_launch_us": round(avg_us, 3), "algorithmic_bytes_per_launch": int(nbytes),
+                           "launches_per_run": int(launches)}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cb = cpu_baseline_gp(prob, args.cpu_max_steps)
         out["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "sample")}
         out["cpu_final_loss"] = cb["final_loss"]
@@ -303,12 +335,12 @@ def run_tracks(args):
     # write the per-track and per-row outputs once
     nbytes = 8 * ne + 12 * nn + 9 * n_tracks + 8 * n_rows
     achieved = nbytes / avg_s / 1e9
-    t0 = time.perf_counter()
-    import contextlib
-    import io
-    with contextlib.redirect_stdout(io.StringIO()):
-        full = TrackEngine(vg, images, device=dev).EstablishFullTracks({'thres_inconsistency': 10.0})
-    e2e = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        # insfm_tracks_establish's outputs (include/insfm_tracks.h), each cut to the length the call reported
+        names = ("track_root", "track_bad", "track_nodes", "row_node", "row_track")
+        sizes = (n_tracks, n_tracks, n_tracks, n_rows, n_rows)
+        dump_outputs(args.dump_outputs, dict({k: o[:n] for k, o, n in zip(names, outs, sizes)},
+                                             counts=[n_tracks, n_rows]))
     out = {
         "metric": "track establishment: inlier matches/s (TrackEngine.EstablishFullTracks core)",
         "value": round(world * ne / dt * args.steps, 1), "unit": "matches/s", "n_gpus": world, "steps": args.steps,
@@ -319,14 +351,22 @@ def run_tracks(args):
                                f"pairs / {ne} inlier matches -> {n_tracks} tracks", "images": len(images),
                    "features": nn, "pairs": len(vg.image_pairs), "matches": ne, "tracks": n_tracks,
                    "parallelism": f"replicas x{world}" if world > 1 else "single GPU"},
-        "tracks_kept": len(full), "end_to_end_s": round(e2e, 3),
         "roofline": {"kernel": "insfm_tracks_establish (whole device pipeline, 15 launches incl. 2 radix sorts)",
                      "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
                      "avg_launch_us": round(avg_s * 1e6, 1), "algorithmic_bytes_per_launch": int(nbytes),
                      "launches_per_run": args.steps},
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full:
+        # the end-to-end EstablishFullTracks (host flattening + device + the reference's dict), a run of its own
+        t0 = time.perf_counter()
+        import contextlib
+        import io
+        with contextlib.redirect_stdout(io.StringIO()):
+            full = TrackEngine(vg, images, device=dev).EstablishFullTracks({'thres_inconsistency': 10.0})
+        e2e = time.perf_counter() - t0
+        out.update(tracks_kept=len(full), end_to_end_s=round(e2e, 3))
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import tracks as OT
         from instantsfm_amd.scene.defs import ViewGraph
         sub = ViewGraph()
@@ -412,7 +452,7 @@ def run_passes(args):
                 raise RuntimeError("pass kernel failed")
     torch.cuda.synchronize(dev)
     kern = {}
-    for name, (fn, nbytes) in calls.items():
+    for name, (fn, nbytes) in calls.items() if args.full else ():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(args.steps):
@@ -429,8 +469,9 @@ def run_passes(args):
             fn()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
-    name = max(kern, key=lambda k: kern[k]["avg_launch_us"])
-    kk = kern[name]
+    if args.dump_outputs:
+        # every filter writes `valid`, so after a step it holds the last one's verdicts (k_reproj_candidates)
+        dump_outputs(args.dump_outputs, {"undistorted": t["out"], "valid_reproj_candidates": t["valid"]})
     out = {
         "metric": "between-round + retriangulation passes: observations/s (6 per-item kernels per step)",
         "value": round(N * args.steps / dt, 1), "unit": "obs/s", "n_gpus": 1, "steps": args.steps,
@@ -439,14 +480,19 @@ def run_passes(args):
         "data": "synthetic (config-3 scene, instantsfm_amd/synth.py; float32 features as a database holds them)",
         "config": {"workload": f"config 3 scene: {C} images / {P} tracks / {N} observations, one pass of each filter",
                    "images": C, "tracks": P, "obs": N, "parallelism": "single GPU"},
-        "kernel_us": {k: v["avg_launch_us"] for k, v in kern.items()}, "kernels": kern,
-        "roofline": {"kernel": name, "bound": "hbm", "achieved": kk["achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(kk["achieved_gbs"] / HBM_PEAK_GBS, 4), "traffic": None,
-                     "avg_launch_us": kk["avg_launch_us"], "algorithmic_bytes_per_launch": kk["algorithmic_bytes_per_launch"],
-                     "launches_per_run": args.steps,
-                     "timing": "torch.cuda.Event on the current stream, which the library launches on"},
     }
-    if not args.no_cpu:
+    if args.full:
+        name = max(kern, key=lambda k: kern[k]["avg_launch_us"])
+        kk = kern[name]
+        out.update({
+            "kernel_us": {k: v["avg_launch_us"] for k, v in kern.items()}, "kernels": kern,
+            "roofline": {"kernel": name, "bound": "hbm", "achieved": kk["achieved_gbs"], "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": round(kk["achieved_gbs"] / HBM_PEAK_GBS, 4), "traffic": None,
+                         "avg_launch_us": kk["avg_launch_us"],
+                         "algorithmic_bytes_per_launch": kk["algorithmic_bytes_per_launch"],
+                         "launches_per_run": args.steps,
+                         "timing": "torch.cuda.Event on the current stream, which the library launches on"}})
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_passes(args.seed)
     print(json.dumps(out), flush=True)
 
@@ -609,7 +655,9 @@ def run_mapper(args):
         "trace": [[t[0], t[1], t[2], None if t[3] is None else float(t[3])] for t in T['trace']],
         "camera_center_err_max": round(center_err, 5), "db_generation_s": round(gen_s, 2),
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"camera_centers": C})
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_mapper(args, tmp, dev)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -666,6 +714,12 @@ def main():
     ap.add_argument("--mapper-points", type=int, default=100_000, help="--path mapper: scene points")
     ap.add_argument("--mapper-runs", type=int, default=1, help="--path mapper: timed mapper runs")
     ap.add_argument("--cpu-edges", type=int, default=1_500_000, help="--path tracks: matches in the CPU sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the instrumented "
+                         "replay (phase split), per-kernel and roofline timings, the end-to-end Solve split and the "
+                         "CPU baseline (--no-solve / --no-cpu drop the last two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy")
     args = ap.parse_args()
     if args.path == "gp":
         return run_gp(args)
@@ -735,6 +789,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss, rmse = eng.cost(cams, pts)
+    if rank == 0 and args.dump_outputs:
+        # what a caller of step() holds after the last timed step: the parameters updated in place and its loss
+        dump_outputs(args.dump_outputs, {"cams": cams, "points": pts, "loss": losses[-1:]})
 
     # stop rule of bundle_adjustment.py:134-141 applied to the timed loss history
     conv_step = None
@@ -744,6 +801,50 @@ def main():
         if abs((b - a) / b) < 5e-4 or h[-1] == h[-2]:
             conv_step = k
             break
+
+    tl = args.precond >= 1
+    C, P, N, D = prob.n_cams, prob.n_points, prob.n_obs, eng.D
+    nnzb = eng.nnzb()
+    trials = sum(s["trials"] for s in stats)
+    out = {
+        "metric": "LM-BA iterations/sec (+ final reprojection RMSE)",
+        "value": round(args.steps / dt, 4),
+        "unit": "LM it/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (seeded scene generator instantsfm_amd/synth.py, SURVEY.md 8(d))",
+        "config": {"workload": f"config {args.config}: synthetic {C}-cam / {P}-point / {N}-obs SIMPLE_RADIAL BA, "
+                               f"LM steps of the full scene" + (", track-sharded" if world > 1 else ""),
+                   "cams": C, "points": P, "obs": N, "camera_block_dim": D, "schur_blocks": nnzb,
+                   "parallelism": f"track-shard x{world}" if world > 1 else "single GPU"},
+        "final_loss": final_loss,
+        "converged_at_step": conv_step,
+        "rmse_after_timed_steps_px": rmse,
+        "pcg_iters": [s["pcg_iters"] for s in stats],
+        "trials": trials,
+        "preconditioner": ("block-Jacobi" if not tl else "two-level (block-Jacobi + camera-cluster similarity coarse space"
+                           + (", A-DEF2 coarse correction from the coarse initial guess)" if args.precond == 2 else ", additive)")),
+        "cg_path": eng.cg_info()[0],
+        "cpu_baseline": None,  # (measured under --full)
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        eng.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        # a plain run ends here: everything below takes device or CPU runs of its own
+        return finish()
 
     # ---- outside the timed region: per-phase breakdown (instrumented replay) and per-kernel device times ----
     eng.reset()
@@ -756,13 +857,9 @@ def main():
         if conv_step is not None and k + 1 == conv_step:
             rmse_conv = eng.cost(ci, pi)[1]
     eng.set_timing(False)
-    tl = args.precond >= 1
-    C, P, N, D = prob.n_cams, prob.n_points, prob.n_obs, eng.D
     Pl = shards[rank][1] - shards[rank][0]
     Nl = int(np.sum((prob.pt_idx >= shards[rank][0]) & (prob.pt_idx < shards[rank][1])))
-    nnzb = eng.nnzb()
     ph = np.sum([s["time_ms"] for s in istats], axis=0)
-    trials = sum(s["trials"] for s in stats)
     cg_launches = sum(s["cg_launches"] for s in stats)
     # which CG the default path runs: the persistent k_tl_cgp (one launch per solve) when this handle is eligible
     cgp = eng.debug_time_cgp(10) if tl else None
@@ -871,41 +968,17 @@ def main():
                        "timing": "back-to-back builds with the full grid on the main stream (hipEvents); on the default "
                                  "path k_tl_cgp writes the segments and only k_tl_ereduce runs"})
 
-    out = {
-        "metric": "LM-BA iterations/sec (+ final reprojection RMSE)",
-        "value": round(args.steps / dt, 4),
-        "unit": "LM it/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (seeded scene generator instantsfm_amd/synth.py, SURVEY.md 8(d))",
-        "config": {"workload": f"config {args.config}: synthetic {C}-cam / {P}-point / {N}-obs SIMPLE_RADIAL BA, "
-                               f"LM steps of the full scene" + (", track-sharded" if world > 1 else ""),
-                   "cams": C, "points": P, "obs": N, "camera_block_dim": D, "schur_blocks": nnzb,
-                   "parallelism": f"track-shard x{world}" if world > 1 else "single GPU"},
-        "final_loss": final_loss,
+    out.update({
         "final_rmse_px": rmse_conv,
-        "converged_at_step": conv_step,
-        "rmse_after_timed_steps_px": rmse,
-        "pcg_iters": [s["pcg_iters"] for s in stats],
-        "trials": trials,
         "phase_ms_per_step": {k: round(float(v) / args.steps, 3) for k, v in
                               zip(["linearize", "k_schur", "linear_solve", "backsub_update", "trial_cost",
                                    "cg_iterations", "coarse_chain_side_stream"], ph)},
         "kernel_us": dict({k: round(v[2], 3) for k, v in kern.items()},
                           **({"k_tl_cgp_iterations": round(cgp[2], 2)}
                              if cgp is not None else {})),
-        "preconditioner": ("block-Jacobi" if not tl else "two-level (block-Jacobi + camera-cluster similarity coarse space"
-                           + (", A-DEF2 coarse correction from the coarse initial guess)" if args.precond == 2 else ", additive)")),
-        "cg_path": eng.cg_info()[0],
         "roofline": roof,
         "roofline_next_kernels": others,
-    }
+    })
     if world > 1 or eng.exchange_calls[0]:
         from instantsfm_amd.engine import CG_PATHS
         xspan = float(ph[7]) / args.steps if len(ph) > 7 else 0.0
@@ -929,12 +1002,7 @@ def main():
         out["cpu_steps_to_converge"] = cb["steps"]
     elif rank == 0:
         out["cpu_baseline"] = None
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    eng.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -9,7 +9,7 @@ for spec in "$@"; do
   for w in $spec; do
     if [[ "$w" == *=* && "$w" != --* ]]; then envs+=("$w"); else args+=("$w"); fi
   done
-  env "${envs[@]}" timeout -k 10 150 python -u bench.py --no-cpu --no-solve "${args[@]}" 2>/dev/null | python3 -c "
+  env "${envs[@]}" timeout -k 10 150 python -u bench.py --full --no-cpu --no-solve "${args[@]}" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('[${spec:--}]', d['value'], 'it/s', d['ms_per_step'], 'ms', 'phases', d['phase_ms_per_step'], 'iters', sum(d['pcg_iters']), 'rmse', d['final_rmse_px'])" || exit 1
