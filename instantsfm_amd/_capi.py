@@ -55,18 +55,23 @@ class Stats(ctypes.Structure):
                     coarse_used=self.coarse_used)
 
 
-# exported symbols (every one declared in include/*.h)
-SYMBOLS = ("insfm_build_info", "insfm_ba_default_desc", "insfm_ba_create", "insfm_ba_step", "insfm_ba_cost", "insfm_ba_reset",
-           "insfm_ba_destroy", "insfm_ba_last_error", "insfm_ba_debug_linearize", "insfm_ba_debug_solve",
-           "insfm_ba_debug_get", "insfm_ba_nnzb", "insfm_ba_exchange_count", "insfm_ba_set_exchange",
-           "insfm_ba_debug_time_kernel", "insfm_ba_set_timing", "insfm_ba_debug_clusters", "insfm_ba_debug_spd_inverse",
-           "insfm_ba_release_cache", "insfm_ba_set_ranks_per_device", "insfm_ba_cg_info", "insfm_ba_set_persistent_cg", "insfm_ba_cg_fallbacks", "insfm_ba_cg_window", "insfm_ba_cg_attach", "insfm_ba_cg_partition",
-           "insfm_ba_debug_time_xchg", "insfm_ba_debug_time_cgp", "insfm_ba_debug_stamps",
-           "insfm_gp_default_desc", "insfm_gp_create", "insfm_gp_step", "insfm_gp_cost", "insfm_gp_debug_linearize",
-           "insfm_gp_debug_get_ds",
-           "insfm_undistort", "insfm_filter_reproj_normalized", "insfm_filter_angle", "insfm_filter_tri_angle",
-           "insfm_filter_reproj_pixel", "insfm_reproj_candidates",
-           "insfm_tracks_establish")
+# exported symbols (every one declared in include/*.h): the product ABI (insfm_ba.h, insfm_gp.h, insfm_passes.h,
+# insfm_tracks.h) and the introspection / prototype entry points of insfm_ba_debug.h
+PUBLIC_SYMBOLS = ("insfm_build_info", "insfm_ba_default_desc", "insfm_ba_create", "insfm_ba_step", "insfm_ba_cost",
+                  "insfm_ba_reset", "insfm_ba_destroy", "insfm_ba_last_error", "insfm_ba_exchange_count",
+                  "insfm_ba_set_exchange", "insfm_ba_set_timing", "insfm_ba_release_cache",
+                  "insfm_ba_set_ranks_per_device", "insfm_ba_cg_info", "insfm_ba_set_persistent_cg",
+                  "insfm_ba_cg_fallbacks",
+                  "insfm_gp_default_desc", "insfm_gp_create", "insfm_gp_step", "insfm_gp_cost",
+                  "insfm_undistort", "insfm_filter_reproj_normalized", "insfm_filter_angle", "insfm_filter_tri_angle",
+                  "insfm_filter_reproj_pixel", "insfm_reproj_candidates",
+                  "insfm_tracks_establish")
+DEBUG_SYMBOLS = ("insfm_ba_debug_linearize", "insfm_ba_debug_solve", "insfm_ba_debug_get", "insfm_ba_nnzb",
+                 "insfm_ba_debug_time_kernel", "insfm_ba_debug_clusters", "insfm_ba_debug_spd_inverse",
+                 "insfm_ba_debug_time_cgp", "insfm_ba_debug_stamps",
+                 "insfm_gp_debug_linearize", "insfm_gp_debug_get_ds",
+                 "insfm_ba_cg_window", "insfm_ba_cg_attach", "insfm_ba_cg_partition", "insfm_ba_debug_time_xchg")
+SYMBOLS = PUBLIC_SYMBOLS + DEBUG_SYMBOLS
 
 _lib = None
 

@@ -33,13 +33,14 @@
 
 #include "../../include/insfm_ba.h"
 #include "../../include/insfm_gp.h"
+#include "../../include/insfm_ba_debug.h"
 #include "ba_device.h"
 #include "ba_common.h"
 #include "ba_twolevel.h"
 #include "ba_cgp.h"
 #include "ba_gp.h"
 #include "cg_poll.h"
-#include "create_host.h"
+#include "create_plan.h"
 
 using namespace insfm;
 
@@ -1556,91 +1557,6 @@ __global__ __launch_bounds__(kFinalThreads) void k_final(const double* __restric
 }
 
 // flags[0..3] = 0, status[0..3] = 0
-// ---- create: structure derived on the device --------------------------------------------------------------------
-// Per local track p (observations sorted by camera): each observation's track and the start of its camera run, i.e.
-// of its upper partners (the tail of the track from there on).
-__global__ __launch_bounds__(kThreads) void k_derive_tracks(int Pl, const int* __restrict__ pt_ptr, const int* __restrict__ cam,
-                                                            int* __restrict__ ptl, int* __restrict__ ustart) {
-    const int p = blockIdx.x * kThreads + threadIdx.x;
-    if (p >= Pl) return;
-    const int b0 = pt_ptr[p], b1 = pt_ptr[p + 1];
-    int u = b0, prev = -1;
-    for (int o = b0; o < b1; ++o) {
-        const int c = cam[o];
-        if (c != prev) { u = o; prev = c; }
-        ptl[o] = p;
-        ustart[o] = u;
-    }
-}
-// Per camera-major entry e (observation o = cam_obs[e]): the Schur descriptor {o, p, partner begin, partner end} and,
-// for the BA, the point and uv the camera linearization reads.
-__global__ __launch_bounds__(kThreads) void k_derive_cm(int Nl, const int* __restrict__ cam_obs, const int* __restrict__ ptl,
-                                                        const int* __restrict__ ustart, const int* __restrict__ pt_ptr,
-                                                        const double* __restrict__ uv, int4* __restrict__ sdesc,
-                                                        int* __restrict__ cm_pt, double* __restrict__ cm_uv) {
-    const int e = blockIdx.x * kThreads + threadIdx.x;
-    if (e >= Nl) return;
-    const int o = cam_obs[e], p = ptl[o];
-    sdesc[e] = make_int4(o, p, ustart[o], pt_ptr[p + 1]);
-    if (uv) {
-        cm_pt[e] = p;
-        reinterpret_cast<double2*>(cm_uv)[e] = reinterpret_cast<const double2*>(uv)[o];
-    }
-}
-
-// Upper block pattern of S and the co-visibility weights on the device (create, single rank; the host pass in create
-// is the multi-rank / INSFM_DIAG=pattern_host path and gives the same lists): one workgroup per camera row i counts, in
-// LDS, for every camera j the (observation of i, observation of j) pairs sharing a track, walking each own
-// observation's upper partners [ustart, track end) exactly like k_schur.  `off` null: cnt[i] = #{j > i with pairs};
-// else the j > i in increasing order and their pair counts go to nb / wt from off[i] (the second pass recounts).
-constexpr int kPatternMaxC = 16384;  // the row's counters in <= 64 KB of LDS
-__global__ __launch_bounds__(256) void k_pattern(int C, const int* __restrict__ cam_ptr, const int* __restrict__ cam_obs,
-                                                 const int* __restrict__ ustart, const int* __restrict__ ptl,
-                                                 const int* __restrict__ pt_ptr, const int* __restrict__ cam,
-                                                 int* __restrict__ cnt, const int* __restrict__ off, int* __restrict__ nb,
-                                                 int* __restrict__ wt) {
-    extern __shared__ int acc[];  // [C]
-    __shared__ int wsum[4];
-    const int i = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    for (int j = t; j < C; j += 256) acc[j] = 0;
-    __syncthreads();
-    for (int e = cam_ptr[i] + t; e < cam_ptr[i + 1]; e += 256) {
-        const int o = cam_obs[e];
-        const int q1 = pt_ptr[ptl[o] + 1];
-        for (int q = ustart[o]; q < q1; ++q) {
-            const int j = cam[q];
-            if (j != i) atomicAdd(&acc[j], 1);  // (the run of camera i itself: the observation and its duplicates)
-        }
-    }
-    __syncthreads();
-    if (!off) {
-        int c = 0;
-        for (int j = i + 1 + t; j < C; j += 256) c += acc[j] > 0;
-        for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-        if (lane == 0) wsum[w] = c;
-        __syncthreads();
-        if (t == 0) cnt[i] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        return;
-    }
-    int base = off[i];
-    for (int j0 = i + 1; j0 < C; j0 += 256) {  // ordered compaction, 256 columns at a time
-        const int j = j0 + t;
-        const int v = j < C ? acc[j] : 0;
-        const unsigned long long bal = __ballot(v > 0);
-        if (lane == 0) wsum[w] = __popcll(bal);
-        __syncthreads();
-        int wo = 0;
-        for (int k = 0; k < w; ++k) wo += wsum[k];
-        if (v > 0) {
-            const int at = base + wo + __popcll(bal & ((1ull << lane) - 1));
-            nb[at] = j;
-            wt[at] = v;
-        }
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
-    }
-}
-
 __global__ void k_zero_words(int* __restrict__ flags, int* __restrict__ status) {
     const int t = threadIdx.x;
     if (t < 4) flags[t] = 0;
@@ -1696,407 +1612,9 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 // ============================================================================================================
 // host side
 // ============================================================================================================
-struct insfm_ba {
-    insfm_ba_desc d{};
-    int model = 0, ni = 0, D = 0, stride = 0;
-    int C = 0, P = 0, N = 0;
-    int p0 = 0, p1 = 0, Pl = 0, o0 = 0, Nl = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    // structure (device)
-    double *uv = nullptr, *pp = nullptr;
-    int *cam = nullptr, *ptl = nullptr, *pt_ptr = nullptr, *cam_ptr = nullptr, *cam_obs = nullptr;
-    int *row_ptr = nullptr, *col = nullptr, *blk_row = nullptr, *ustart = nullptr;
-    int *nbr_ptr = nullptr, *nbr_j = nullptr, *pos_up = nullptr, *pos_lo = nullptr;
-    int4* sdesc = nullptr;  // k_schur: per camera-major own observation {o, p, partner begin, partner end}
-    int* cm_pt = nullptr;    // k_lin_cams: per camera-major observation, its (local) point
-    int* lin_blk = nullptr;  // k_lin_points: track runs of at most kThreads observations (or one longer track)
-    int n_lin = 0;
-    double* cm_uv = nullptr; // k_lin_cams: per camera-major observation, its uv
-    double* Sn = nullptr;  // row-contiguous scaled neighbour blocks for the CG (both triangles, padded rows)
-    int64_t n_nbr = 0;
-    int nbr_stride = 0;  // > 0: every CG row has exactly nbr_stride neighbour slots (padded), row r starts at r * stride
-    bool flags_dirty = false;  // a solve's point preparation ran and no k_final has consumed (cleared) its flag yet
-    int keep_S = 0;      // debug entry points: every solve forms the scaled copy Sn (insfm_ba_debug_get(5) reads S~ from it;
-                         // S itself stays unscaled -- k_tl_cgp reads it)
-    std::vector<int> pos_up_host;  // [nnzb] Sn slot of each upper block (debug_get(5))
-    int4* work = nullptr;
-    int nwork = 0, nnzb = 0, max_chunk = 0;
-    size_t schur_lds = 0;
-    // numeric (device)
-    // W: the BA's symmetric records Y_o = W_o L_p (PointPrep; global positioning: its {u, beta^2} records); y: z_p
-    // (BA) / y_p (GP); Rf: R_p of the first trial's damped point blocks; Mp: M_p of a retried trial
-    double *W = nullptr, *V = nullptr, *gp = nullptr, *Vinv = nullptr, *y = nullptr, *dp = nullptr;
-    double *Rf = nullptr, *Mp = nullptr;
-    double *xbuf = nullptr;  // [S | b | U | gc | scal]
-    double *S = nullptr, *b = nullptr, *U = nullptr, *gc = nullptr, *scal = nullptr;
-    int64_t xcount = 0;
-    double *Lf = nullptr, *Li = nullptr, *dc = nullptr;
-    double* cgmem = nullptr;
-    CgBufs cg{};
-    int cg_nwg = 0;
-    double *cams_cur = nullptr, *cams_new = nullptr, *pts_cur = nullptr, *pts_new = nullptr;
-    bool ext_cur = false;  // during insfm_ba_step: cams_cur / pts_cur are the caller's buffers
-    bool trial_copied = false;  // the last trial cost's k_publish copied the accepted trial into cams_cur / pts_cur
-    double *part_cost = nullptr, *part_gp = nullptr, *part_gc = nullptr;
-    int n_cost = 0, n_gp = 0, n_gc = 0;
-    int n_gp_grp = 0;  // global positioning: k_gp_backsub blocks (kGPG lanes per track)
-    double* result = nullptr;
-    int* flags = nullptr;
-    double* host_res = nullptr;  // pinned 128 B: result[0..4] (doubles) | cg status (ints, from double slot 8)
-    int* prog_host = nullptr;    // pinned, device-mapped: progress of the two-level CG (CgBufs::prog)
-    // the last linearization already prepared the points (Vinv, y, status) for damping factor prep_f (PointPrep)
-    bool prep_valid = false;
-    double prep_f = 0.0;
-    double* pub_host = nullptr;  // pinned, device-mapped: k_publish's result[0..4], decision, sequence word (double 8)
-    double* pub_dev = nullptr;
-    unsigned pub_seq = 0;
-    std::vector<void*> allocs;
-    // LM state
-    double damping = 0.0, down = 0.0, loss = 0.0;
-    bool have_loss = false;
-    int last_cg_iters = 16;
-    hipEvent_t ev[18]{};  // 0-9 phase markers, 10-11 debug timing, 12-15 the side chain's start / end by slot,
-                          // 16-17 the chunked exchange's span on the exchange stream
-    bool chain_timed[2]{};  // set_timing: the side chain of that slot has timing events not yet harvested
-    bool timing = false;
-    // device time of the current step, accumulated per phase (ms): see insfm_ba_stats.time_ms
-    double tms[8]{};
-    int cg_launches = 0;
-    bool want_timing = false;       // insfm_ba_set_timing: hipEvent phase timing inside insfm_ba_step
-    // two-level preconditioner (desc.precond == 1)
-    bool tlon = false;
-    TlBufs tl{};
-    std::vector<int> clab_host;
-    size_t erow_lds = 0, pc_lds = 0;
-    int pc_rows = 0;  // k_tl_pc rows per restriction pass
-    // the register-resident persistent CG (ba_cgp.h k_tl_cgp): blocks per row (0: not eligible), grid, the w exchange
-    // [C][8], the coarse vector [kCoarseMax], the grid-barrier words; cgp_defer: the side chain of slot cgp_slot is
-    // issued behind the CG (k_tl_cgp holds every SIMD of its CUs, so a chain beside it would crawl on the rest)
-    int cgp_nb = 0, cgp_grid = 0, cgp_slot = 0;
-    bool cgp_det = false;                // fixed-order partial sums (deterministic mode, multi-rank replicated CG)
-    bool adef2 = false;                  // precond 2: k_tl_cgp applies the coarse correction as A-DEF2 (ba_cgp.h)
-    bool basis_by_factor = false;        // this solve's coarse basis was formed by k_cg_factor_basis
-    int adef2_fallbacks = 0;             // A-DEF2 solves that broke down and were repeated additively (adef2_fallback)
-    double* cgp_runs = nullptr;               // [2][grid * 4][12] the cluster runs' partials by parity (cgp_det)
-    int* cgp_src = nullptr;     // [n_nbr] S block of each CG slot: e (upper), ~e (lower, transposed), INT_MIN (pad)
-    bool sn_valid = false;      // Sn holds the scaled S~ of the current solve (k_cg_scale ran for it)
-    long long* stamps = nullptr;  // INSFM_DIAG=stamps: [kStampSteps][kStKinds][2] kernel entry / exit (wall_clock64)
-    long long stamp_step = 0;     // LM steps stamped so far
-    unsigned cgp_epochs = 0;  // grid barriers the counters in cgp_sync have counted (reset with them)
-    bool cgp_defer = false;
-    int cgp_slots = 0;            // workgroups of k_tl_cgp the device holds at once
-    bool cg_async = false;        // lm_step: a k_tl_cgp solve's status is read after the trial's k_publish
-    bool cgp_pending = false;     // a k_tl_cgp launch whose status the host has not read yet (cgp_complete)
-    bool dc_by_cgp = false;       // this solve's k_tl_cgp writes dc itself (cg_tail launches no k_cg_finish)
-    bool cgp_lost = false;        // the last k_tl_cgp timed out at a grid barrier (another process holds CUs)
-    double* cgp_trace = nullptr;  // INSFM_DIAG=cgp_trace: [64][4] of the last solve, printed to stderr
-    // row-partitioned multi-rank CG (ba_xpart.h; insfm_ba_cg_window / insfm_ba_cg_attach)
-    bool xpart = false;
-    double* xwin = nullptr;            // own window (uncached): 2 x [vc C*D | gd 3C | rowR C*MC + 2], xg C*D, flags
-    size_t xwin_bytes = 0;
-    long long xoff_region[2]{}, xoff_xg = 0, xoff_flags = 0;  // in doubles from the window base
-    std::vector<void*> xopened;        // IPC-opened peer windows (closed at destroy)
-    double** xbases = nullptr;         // device [world] window bases (own included)
-    unsigned** xpflags = nullptr;      // device [world] flag blocks
-    unsigned* xcnt = nullptr;          // device exchange counters [2]
-    std::vector<int> xq;               // [world + 1] cluster-ordered row ranges of the ranks
-    double* cgp_wx = nullptr;           // [2][C][8]
-    unsigned long long* cgp_yg = nullptr;  // [kCoarseMax][2] tagged granules of y
-    unsigned cgp_tag = 1;               // tag of the next launch's first iteration
-    unsigned* cgp_sync = nullptr;
-    bool chain_oseg = false;  // the side chain of slot cgp_slot builds E from k_tl_cgp's segments (reissue_chain)
-    // the coarse factorization of solve n runs on `side` while the CG of solve n uses slot (n-1)&1
-    double *Ebuf[2]{}, *Einvbuf[2]{};
-    double* gjW = nullptr;  // Gauss-Jordan ping-pong buffer [ldE][ldE]
-    double* gjP = nullptr;  // Gauss-Jordan pivot-block inverses [2][64][64]
-    int* okbuf = nullptr;  // [2]
-    hipStream_t side = nullptr;
-    hipEvent_t ev_E = nullptr, ev_built = nullptr, ev_fact[2]{};
-    // chunked [S | b] exchange (desc.allreduce_async): work-item / row boundaries of the chunks, the exchange stream
-    std::vector<int> xw, xr, rptr_host;
-    hipStream_t xstream = nullptr;
-    // u_late: k_lin_cams runs on `aux` beside k_lin_points / k_schur; k_schur builds S / b without U / g_c and
-    // k_cg_factor adds them after waiting for ev_lc (lin_join).  Single-rank W-path only.
-    bool u_late = false, lin_pending = false;
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_lin0 = nullptr, ev_lc = nullptr;
-    hipEvent_t ev_x = nullptr, ev_xdone = nullptr;
-    hipEvent_t ev_pre = nullptr;  // multi-rank: recorded in front of the CG (its stall deadline starts after it)
-    bool built_pending = false;
-    long long tl_solves = 0;
-    bool tl_fresh = false;  // no solve since the last linearization (the lag rule applies to that solve only)
-    int coarse_used = 0;
-    // global positioning (kind 1, insfm_gp_*): per local observation ray / scale-free flag / source index, camera
-    // factors, the linearization records and the scale-eliminated camera blocks of the current trial
-    int kind = 0;
-    double *trans = nullptr, *fcam = nullptr, *gobs = nullptr, *Up = nullptr, *gpc = nullptr, *VY = nullptr;
-    int *sfree = nullptr, *osrc = nullptr;
-    double *scl_cur = nullptr, *scl_new = nullptr, *ds = nullptr;
-    std::vector<int> osrc_host;
-    std::vector<std::pair<const char*, double>> hmarks;  // INSFM_HOST_TRACE=2
-};
+#include "ba_handle.h"
 
 namespace {
-
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            h->err = std::string(#expr) + " failed: " + hipGetErrorString(e_);                    \
-            return INSFM_BA_EHIP;                                                                 \
-        }                                                                                         \
-    } while (0)
-
-// INSFM_DIAG: comma-separated diagnostics, read once per process (none is on by default):
-//   poison        every buffer dalloc hands out is first filled with 0xff bytes (NaN doubles, -1 ints), so a read of
-//                 something never written shows up instead of a fresh allocation's zero pages
-//   pattern_host  create builds the block pattern by the host pass (the multi-rank path) on a single rank too
-//   trace         per solve, host microseconds spent enqueueing CG iterations (stderr)
-//   trace2        per LM step, host timestamps of the step's API calls (stderr)
-//   create        host milliseconds of create's phases (stderr)
-//   no_cgp        the two-level CG runs as two launches per iteration (k_tl_pc_cl + k_tl_pspmv) even where the
-//                 persistent register-resident k_tl_cgp is eligible (A/B and parity of the two paths)
-//   cgp_trace     k_tl_cgp records gamma, delta, rho and its stop flag per iteration; printed after each solve
-//   cgp128        k_tl_cgp with 128 register blocks per row even for shorter rows (tests the wide variant)
-//   own_streams   per-handle side / linearization streams instead of the process-wide ones (A/B)
-//   chain_hold    timing only: the lagged coarse-inverse chain is never issued (later solves keep an older E^-1)
-//   side_hi / side_normal   the coarse-inverse side stream at the high / normal stream priority (default: lowest)
-bool diag(const char* name) {
-    static const std::string v = [] { const char* e = std::getenv("INSFM_DIAG"); return std::string(e ? e : ""); }();
-    const size_t n = std::strlen(name);
-    for (size_t a = 0; a <= v.size();) {
-        size_t b = v.find(',', a);
-        if (b == std::string::npos) b = v.size();
-        if (b - a == n && v.compare(a, n, name) == 0) return true;
-        a = b + 1;
-    }
-    return false;
-}
-
-// Process-wide cache of the device buffers of destroyed handles.  TorchBA creates a handle per Solve (the mapper
-// solves 4-5 times per reconstruction), and freeing config 3's ~1 GB of buffers took ~7 ms per destroy (hipFree
-// synchronizes the device) plus the allocations of the next create.  insfm_ba_destroy waits for the handle's streams
-// and parks its buffers here, keyed by their HIP device; dalloc takes the smallest parked buffer of the current device
-// of at least the requested size and at most twice it.  Bounded by INSFM_DEVICE_CACHE_MB (default 4096; 0 disables
-// it): beyond that, buffers are freed.  The parked memory is invisible to PyTorch's caching allocator, so
-// insfm_ba_release_cache() frees it all (TorchBA calls it when torch reports an out-of-memory error, the mapper at the
-// end of a reconstruction); a failing hipMalloc inside dalloc releases it too.
-struct DeviceCache {
-    struct Buf {
-        size_t bytes;
-        int dev;
-        bool uc;  // uncached device memory (hipDeviceMallocUncached)
-    };
-    std::mutex m;
-    std::map<std::pair<int, size_t>, std::vector<void*>> free;  // (2 * device + uncached, size) -> pointers
-    size_t bytes = 0;
-    std::unordered_map<void*, Buf> info;  // every pointer dalloc handed out (cached or fresh)
-};
-DeviceCache& device_cache() {
-    static DeviceCache* c = new DeviceCache();  // (never destroyed: buffers may be parked until process exit)
-    return *c;
-}
-size_t device_cache_cap() {
-    static const size_t v = [] {
-        const char* e = std::getenv("INSFM_DEVICE_CACHE_MB");
-        return (size_t)(e ? std::max(0LL, std::atoll(e)) : 4096LL) << 20;
-    }();
-    return v;
-}
-
-// frees every parked buffer (any device); returns the bytes released
-size_t release_cache() {
-    DeviceCache& c = device_cache();
-    std::vector<std::pair<void*, int>> drop;
-    size_t n = 0;
-    {
-        std::lock_guard<std::mutex> lk(c.m);
-        for (auto& kv : c.free)
-            for (void* q : kv.second) {
-                drop.emplace_back(q, kv.first.first / 2);
-                c.info.erase(q);
-            }
-        c.free.clear();
-        n = c.bytes;
-        c.bytes = 0;
-    }
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto& d : drop) {
-        if (d.second != cur) (void)hipSetDevice(d.second);
-        (void)hipFree(d.first);
-        if (d.second != cur) (void)hipSetDevice(cur);
-    }
-    (void)hipGetLastError();
-    return n;
-}
-
-// Process-wide helper streams, one per (HIP device, role): the side stream of the coarse-inverse chain (role 0, low
-// priority) and the camera-linearization stream (role 1).  Every handle of a device shares them, so the number of
-// hardware queues a process uses does not grow with the handles alive at once.  With per-handle streams, a TorchBA.Solve
-// run while another config-3 handle was alive (bench.py's solve_end_to_end beside its main engine) took 1.9-2.0 ms per
-// LM step instead of 1.17: its side chain landed on a queue that the dispatcher served behind k_schur, k_gj_step ran
-// 2-4x longer, and the main stream waited ~330 us per step for the lagged coarse inverse (profiles/r5_v1/).  Handles
-// on one device are driven one at a time (the reference builds a TorchBA per Solve, global_mapper.py:115), and all
-// cross-stream ordering is by the handle's own events, so sharing only serializes what would compete anyway.
-// INSFM_DIAG=own_streams restores per-handle streams (A/B).
-std::mutex& stream_pool_mutex() {
-    static std::mutex* m = new std::mutex();
-    return *m;
-}
-std::map<std::pair<int, int>, hipStream_t>& stream_pool() {
-    static auto* p = new std::map<std::pair<int, int>, hipStream_t>();  // (never destroyed, like the device cache)
-    return *p;
-}
-hipError_t helper_stream(int role, int prio, hipStream_t* out) {
-    if (diag("own_streams")) return hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    std::lock_guard<std::mutex> lk(stream_pool_mutex());
-    auto& pool = stream_pool();
-    auto it = pool.find(std::make_pair(dev, role));
-    if (it != pool.end()) {
-        *out = it->second;
-        return hipSuccess;
-    }
-    const hipError_t e = hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio);
-    if (e == hipSuccess) pool[std::make_pair(dev, role)] = *out;
-    return e;
-}
-void release_helper_stream(hipStream_t s) {
-    if (!s) return;
-    {
-        std::lock_guard<std::mutex> lk(stream_pool_mutex());
-        for (auto& kv : stream_pool())
-            if (kv.second == s) return;  // pooled: stays for the next handle
-    }
-    (void)hipStreamDestroy(s);
-}
-
-// uc: uncached device memory (the CG's cross-workgroup hand-off buffers: their loads, stores and atomics skip the L2s,
-// config 3: 10.4-11.0 -> 9.3-9.7 us per k_tl_cgp iteration; profiles/r4_v7/)
-int dalloc(insfm_ba* h, void** p, size_t bytes, bool uc = false) {
-    if (bytes == 0) bytes = 16;
-    bytes = (bytes + 255) & ~(size_t)255;
-    DeviceCache& c = device_cache();
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    const int key = 2 * dev + (uc ? 1 : 0);
-    bool hit = false;
-    {
-        std::lock_guard<std::mutex> lk(c.m);
-        auto it = c.free.lower_bound(std::make_pair(key, bytes));
-        if (it != c.free.end() && it->first.first == key && it->first.second <= 2 * bytes && !it->second.empty()) {
-            *p = it->second.back();
-            it->second.pop_back();
-            c.bytes -= it->first.second;
-            if (it->second.empty()) c.free.erase(it);
-            hit = true;
-        }
-    }
-    if (hit) {
-        h->allocs.push_back(*p);
-        if (diag("poison")) (void)hipMemset(*p, 0xff, bytes);
-        return 0;
-    }
-    auto alloc = [&] { return uc ? hipExtMallocWithFlags(p, bytes, hipDeviceMallocUncached) : hipMalloc(p, bytes); };
-    hipError_t e = alloc();
-    if (e == hipErrorOutOfMemory) {  // give the parked buffers back and try once more
-        (void)hipGetLastError();
-        release_cache();
-        e = alloc();
-    }
-    if (e != hipSuccess) {
-        h->err = std::string("hipMalloc(") + std::to_string(bytes) + ") failed: " + hipGetErrorString(e);
-        return INSFM_BA_ENOMEM;
-    }
-    {
-        std::lock_guard<std::mutex> lk(c.m);
-        c.info[*p] = DeviceCache::Buf{bytes, dev, uc};
-    }
-    h->allocs.push_back(*p);
-    if (diag("poison")) (void)hipMemset(*p, 0xff, bytes);
-    return 0;
-}
-
-// the handle's buffers back to the cache (the caller has synchronized every stream that used them)
-void dfree_all(insfm_ba* h) {
-    DeviceCache& c = device_cache();
-    const size_t cap = device_cache_cap();
-    std::vector<void*> drop;
-    {
-        std::lock_guard<std::mutex> lk(c.m);
-        for (void* q : h->allocs) {
-            auto it = c.info.find(q);
-            if (it == c.info.end()) { drop.push_back(q); continue; }
-            const DeviceCache::Buf b = it->second;
-            if (c.bytes + b.bytes > cap) {
-                c.info.erase(it);
-                drop.push_back(q);
-            } else {
-                c.free[std::make_pair(2 * b.dev + (b.uc ? 1 : 0), b.bytes)].push_back(q);
-                c.bytes += b.bytes;
-            }
-        }
-    }
-    for (void* q : drop) (void)hipFree(q);  // (hipFree takes a pointer of any device)
-    h->allocs.clear();
-}
-
-template <typename T>
-int upload(insfm_ba* h, T** dst, const T* src, size_t n) {
-    int rc = dalloc(h, (void**)dst, n * sizeof(T));
-    if (rc) return rc;
-    if (n) HIPCHK(hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
-    return 0;
-}
-
-int model_ni(int m) {
-    switch (m) {
-        case 0: return 1; case 1: return 2; case 2: return 2; case 3: return 3; case 4: return 6;
-        case 5: return 6; case 6: return 10; case 8: return 2; case 9: return 3;
-        default: return -1;
-    }
-}
-
-// ---- model / D dispatch ----------------------------------------------------------------------------------------
-template <typename F>
-int with_model(int m, F&& f) {
-    switch (m) {
-        case 0: return f(std::integral_constant<int, 0>{});
-        case 1: return f(std::integral_constant<int, 1>{});
-        case 2: return f(std::integral_constant<int, 2>{});
-        case 3: return f(std::integral_constant<int, 3>{});
-        case 4: return f(std::integral_constant<int, 4>{});
-        case 5: return f(std::integral_constant<int, 5>{});
-        case 6: return f(std::integral_constant<int, 6>{});
-        case 8: return f(std::integral_constant<int, 8>{});
-        case 9: return f(std::integral_constant<int, 9>{});
-        default: return INSFM_BA_EINVAL;
-    }
-}
-template <typename F>
-int with_D(int D, F&& f) {
-    switch (D) {
-        case 3: return f(std::integral_constant<int, 3>{});  // global positioning
-        case 7: return f(std::integral_constant<int, 7>{});
-        case 8: return f(std::integral_constant<int, 8>{});
-        case 9: return f(std::integral_constant<int, 9>{});
-        case 12: return f(std::integral_constant<int, 12>{});
-        case 16: return f(std::integral_constant<int, 16>{});
-        default: return INSFM_BA_EINVAL;
-    }
-}
-
-int launch_err(insfm_ba* h, const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->err = std::string(what) + ": " + hipGetErrorString(e);
-        return INSFM_BA_EHIP;
-    }
-    return 0;
-}
 
 int allreduce(insfm_ba* h, double* buf, int64_t n) {
     // a single rank skips the exchange unless a callback is installed (tests drive the RCCL path with one rank)
@@ -2137,77 +1655,6 @@ void acc_time(insfm_ba* h, int a, int b, int slot) {
     if (!h->timing) return;
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, h->ev[a], h->ev[b]) == hipSuccess) h->tms[slot] += ms;
-}
-
-// ---- camera clusters of the two-level preconditioner (same rules as oracle/ba_oracle.c: ora_aggregate) ----------
-// Co-visibility weight w(i,j) = number of (obs of i, obs of j) pairs sharing a track.  Greedy aggregation from seeds
-// in increasing id, growing by the most-connected unassigned camera (ties: smallest id) up to K members; aggregates
-// smaller than K/2 are dissolved into the most-connected aggregate of size >= K/2 (ties: smallest aggregate id);
-// labels renumbered by first appearance.
-// (built in create's block-pattern pass)
-struct CovisGraph {
-    std::vector<int> ptr, nb;
-    std::vector<long long> w;
-};
-
-int aggregate(const CovisGraph& g, int C, int K, std::vector<int>& lab) {
-    lab.assign(C, -1);
-    std::vector<long long> score(C, 0);
-    std::vector<char> incand(C, 0);
-    std::vector<int> cand, asize;
-    int nagg = 0;
-    for (int seed = 0; seed < C; ++seed) {
-        if (lab[seed] >= 0) continue;
-        cand.clear();
-        int size = 0, cur = seed;
-        for (;;) {
-            lab[cur] = nagg;
-            ++size;
-            for (int e = g.ptr[cur]; e < g.ptr[cur + 1]; ++e) {
-                const int j = g.nb[e];
-                if (lab[j] >= 0) continue;
-                if (!incand[j]) { incand[j] = 1; score[j] = 0; cand.push_back(j); }
-                score[j] += g.w[e];
-            }
-            if (size >= K) break;
-            int best = -1;
-            long long bs = 0;
-            for (int j : cand) {
-                if (lab[j] >= 0) continue;
-                if (score[j] > bs || (score[j] == bs && bs > 0 && j < best)) { bs = score[j]; best = j; }
-            }
-            if (best < 0) break;
-            cur = best;
-        }
-        for (int j : cand) incand[j] = 0;
-        asize.push_back(size);
-        ++nagg;
-    }
-    const int minsz = K / 2 > 1 ? K / 2 : 1;
-    std::vector<long long> to(nagg, 0);
-    std::vector<int> nl(lab);
-    for (int i = 0; i < C; ++i) {
-        if (asize[lab[i]] >= minsz) continue;
-        for (int e = g.ptr[i]; e < g.ptr[i + 1]; ++e) {
-            const int a = lab[g.nb[e]];
-            if (asize[a] >= minsz) to[a] += g.w[e];
-        }
-        int best = -1;
-        long long bs = 0;
-        for (int e = g.ptr[i]; e < g.ptr[i + 1]; ++e) {
-            const int a = lab[g.nb[e]];
-            if (asize[a] >= minsz && to[a] > 0 && (to[a] > bs || (to[a] == bs && a < best))) { bs = to[a]; best = a; }
-        }
-        for (int e = g.ptr[i]; e < g.ptr[i + 1]; ++e) to[lab[g.nb[e]]] = 0;
-        if (best >= 0) nl[i] = best;
-    }
-    std::vector<int> ren(nagg, -1);
-    int nc = 0;
-    for (int i = 0; i < C; ++i) {
-        if (ren[nl[i]] < 0) ren[nl[i]] = nc++;
-        lab[i] = ren[nl[i]];
-    }
-    return nc;
 }
 
 // ---- phases --------------------------------------------------------------------------------------------------
@@ -2334,7 +1781,7 @@ int run_tl_build(insfm_ba* h, int slot, hipStream_t stream, bool have_oseg = fal
         constexpr int DV = decltype(dc_)::value;
         const int grid = stream != h->stream ? std::min(C, kErowGrid) : C;
         if (!have_oseg)  // (k_tl_cgp wrote the segments of this solve)
-            k_tl_erow<DV><<<grid, kThreads, h->erow_lds, stream>>>(C, h->nbr_ptr, h->nbr_j, h->Sn, tl);
+            k_tl_erow<DV><<<grid, kThreads, 0, stream>>>(C, h->nbr_ptr, h->nbr_j, h->Sn, tl);
         k_tl_ereduce<DV><<<cdiv(m * m, kThreads), kThreads, 0, stream>>>(tl);
         return launch_err(h, "k_tl_erow/ereduce");
     });
@@ -3426,889 +2873,7 @@ int64_t insfm_ba_release_cache(void) { return (int64_t)release_cache(); }
 
 }  // extern "C"
 
-namespace {
-
-// Shared creation of a BA (kind 0: obs = uv [N,2], cpar = pp [C,2]) or global-positioning (kind 1: obs = rays [N,3],
-// cpar = camera factors [C], sfree = scale-free flags [N] or NULL) handle.
-int create_impl(const insfm_ba_desc* desc, int kind, const double* obs, const int32_t* cam_idx, const int32_t* pt_idx,
-                const double* cpar, const int32_t* sfree_in, void* stream, insfm_ba** out) {
-    if (!desc || !out) return INSFM_BA_EINVAL;
-    *out = nullptr;
-    insfm_ba* h = new insfm_ba();
-    h->d = *desc;
-    h->kind = kind;
-    h->stream = reinterpret_cast<hipStream_t>(stream);
-    auto fail = [&](int rc, const std::string& msg) {
-        if (!msg.empty()) h->err = msg;
-        *out = h;  // handle returned so the caller can read the error; caller destroys it
-        return rc;
-    };
-    if (kind == 1) {
-        h->model = kGP;
-        h->ni = 0;
-        h->D = 3;
-        h->stride = 3;
-        h->d.optimize_poses = 1;
-    } else {
-        h->model = desc->cam_model;
-        h->ni = model_ni(h->model);
-        if (h->ni < 0) return fail(INSFM_BA_EINVAL, "unsupported camera model " + std::to_string(h->model));
-        h->D = 6 + h->ni;
-        h->stride = 7 + h->ni;
-    }
-    h->C = desc->n_cams; h->P = desc->n_points; h->N = desc->n_obs;
-    if (h->C <= 0 || h->P <= 0 || h->N < 0) return fail(INSFM_BA_EINVAL, "empty problem");
-    if (!obs || !cam_idx || !pt_idx || !cpar) return fail(INSFM_BA_EINVAL, "null input pointer");
-    if (desc->world_size < 1 || desc->rank < 0 || desc->rank >= desc->world_size) return fail(INSFM_BA_EINVAL, "bad rank");
-    if (desc->world_size > 1 && !desc->allreduce) return fail(INSFM_BA_EINVAL, "world_size > 1 needs allreduce");
-    if (h->C > 30000) return fail(INSFM_BA_EINVAL, "n_cams > 30000 not supported (LDS slot table)");
-    // desc.schur_variant: only 0 (the W-reading k_schur) remains.  Variants 1 / 2 (camera-point blocks re-derived per
-    // pair, LDS-atomic rows / MFMA register accumulation) and 3 (compact W records) were built, parity-tested and
-    // measured slower or even in rounds 2-3; they live in the git history.
-    if (desc->schur_variant != 0) return fail(INSFM_BA_EINVAL, "schur_variant must be 0");
-    const int C = h->C, P = h->P, N = h->N, D = h->D;
-    // every pass over the observations below runs on this pool (create_host.h); joined when create returns
-    HostPool pool(host_pool_size());
-    {
-        // input checks, first failing index wins (the lowest slice with a failure holds it)
-        std::vector<int> bad(pool.size(), 0);
-        pool.ranges(N, [&](int t, long long a, long long b) {
-            for (long long i = a; i < b; ++i) {
-                if (cam_idx[i] < 0 || cam_idx[i] >= C) { bad[t] = 1; return; }
-                if (pt_idx[i] < 0 || pt_idx[i] >= P) { bad[t] = 2; return; }
-                if (i && pt_idx[i] < pt_idx[i - 1]) { bad[t] = 3; return; }
-            }
-        });
-        for (int e : bad) {
-            if (e == 1) return fail(INSFM_BA_EINVAL, "cam_idx out of range");
-            if (e == 2) return fail(INSFM_BA_EINVAL, "pt_idx out of range");
-            if (e == 3) return fail(INSFM_BA_EINVAL, "observations must be track-major (pt_idx nondecreasing)");
-        }
-    }
-    h->p0 = std::max(0, desc->shard_point_begin);
-    h->p1 = desc->shard_point_end < 0 ? P : std::min(P, desc->shard_point_end);
-    if (h->p1 < h->p0) return fail(INSFM_BA_EINVAL, "bad shard range");
-    h->Pl = h->p1 - h->p0;
-    // INSFM_DIAG=create: host milliseconds of create's phases (stderr)
-    static const bool ctrace = diag("create");
-    const double ct0 = wall_seconds();
-    auto tick = [&](const char* what) {
-        if (ctrace) std::fprintf(stderr, "[insfm create] %-28s %8.1f ms\n", what, 1e3 * (wall_seconds() - ct0));
-    };
-    // global track pointers (pt_idx is nondecreasing: one binary search per track)
-    std::vector<int> gptr(P + 1, 0);
-    pool.ranges(P + 1, [&](int, long long a, long long b) {
-        for (long long p = a; p < b; ++p) gptr[p] = (int)(std::lower_bound(pt_idx, pt_idx + N, (int32_t)p) - pt_idx);
-    });
-    h->o0 = gptr[h->p0];
-    h->Nl = gptr[h->p1] - h->o0;
-    const int o0 = h->o0, Nl = h->Nl, Pl = h->Pl;
-    // local arrays; each track's observations are reordered by camera (stable insertion sort: tracks are short) so
-    // that the upper-triangle partners of an observation are the contiguous tail [ustart[o], track end) of its track;
-    // key = that tail's length (the observation's upper-partner count)
-    std::vector<int> lptr(Pl + 1);
-    nivec<int> lptl(Nl), lcam(Nl), lsrc(Nl), lust(Nl), key(Nl);
-    for (int p = 0; p <= Pl; ++p) lptr[p] = gptr[h->p0 + p] - o0;
-    std::vector<int> kmax_t(pool.size(), 0);
-    pool.ranges(Pl, [&](int t, long long pa, long long pb) {
-        int km = 0;
-        for (long long p = pa; p < pb; ++p) {
-            const int b0 = lptr[p], b1 = lptr[p + 1];
-            for (int o = b0; o < b1; ++o) {
-                const int x = o0 + o, cx = cam_idx[x];
-                int u = o;
-                while (u > b0 && cam_idx[lsrc[u - 1]] > cx) { lsrc[u] = lsrc[u - 1]; --u; }
-                lsrc[u] = x;
-            }
-            int u = b0;
-            for (int o = b0; o < b1; ++o) {
-                lcam[o] = cam_idx[lsrc[o]];
-                lptl[o] = (int)p;
-                if (o > b0 && lcam[o] != lcam[o - 1]) u = o;
-                lust[o] = u;
-                key[o] = b1 - u;
-                km = std::max(km, key[o]);
-            }
-        }
-        kmax_t[t] = km;
-    });
-    const int kmax = *std::max_element(kmax_t.begin(), kmax_t.end());
-    tick("local track order");
-    // camera-major lists: within a camera the observations in point order, cut into chunks of kSchurChunk k_schur
-    // rounds (4 x 64 own observations for D = 8), each chunk sorted by descending upper-partner count (stable;
-    // balances the Schur groups of a wave: 2.8 % more wave partner slots than a global count sort, 10.8 % with
-    // one-round chunks).  Every k_schur row then walks the points in the same global order at about the same pace, so
-    // rows running together read a shared track's partner W records close together in time.  Config 3, k_schur:
-    // 491 us (count sort over the whole camera) -> 467 us (chunks of 4 rounds; 1 / 2 / 8 / 16 rounds: 541 / 499 / 471 /
-    // 483 us -- the wave partner slots cost more than the locality buys below 4).  Measured and dropped in round 3
-    // (DESIGN.md section 8): the chunk's slices dealt to the waves in snake order (480-484 vs 473-475 us) and runs of
-    // consecutive rows per XCD (L2 hit 4 -> 54 %, yet 469-515 us).
-    std::vector<int> cptr;
-    nivec<int> cobs;
-    {
-        // observations are track-major (point order), so a stable counting sort by camera leaves each list in point
-        // order; then a stable sort of each chunk by descending partner count
-        pcount_sort(pool, Nl, C, nullptr, [&](int o) { return lcam[o]; }, cobs, cptr);
-        const int NG = 64 / D, K = kSchurChunk * kSchurWaves * NG;
-        pool.ranges(C, [&](int, long long i0, long long i1) {
-            for (long long i = i0; i < i1; ++i)
-                for (int a = cptr[i]; a < cptr[i + 1]; a += K) {
-                    const int e = std::min(a + K, cptr[i + 1]);
-                    std::stable_sort(cobs.data() + a, cobs.data() + e, [&](int x, int y) { return key[x] > key[y]; });
-                }
-        });
-    }
-    (void)kmax;
-    tick("camera-major lists");
-    // the per-observation arrays go to the device now: the block pattern below is derived there (single rank)
-    int rc;
-    if (kind == 1) {
-        nivec<double> tl((size_t)3 * Nl);
-        nivec<int> sl(Nl);
-        pool.ranges(Nl, [&](int, long long a, long long b) {
-            for (long long o = a; o < b; ++o) {
-                for (int k = 0; k < 3; ++k) tl[3 * (size_t)o + k] = obs[3 * (size_t)lsrc[o] + k];
-                sl[o] = sfree_in ? (sfree_in[lsrc[o]] != 0) : 1;
-            }
-        });
-        if ((rc = upload(h, &h->trans, tl.data(), tl.size()))) return fail(rc, "");
-        if ((rc = upload(h, &h->sfree, sl.data(), sl.size()))) return fail(rc, "");
-        if ((rc = upload(h, &h->fcam, cpar, (size_t)C))) return fail(rc, "");
-        if ((rc = upload(h, &h->osrc, lsrc.data(), lsrc.size()))) return fail(rc, "");
-        h->osrc_host.assign(lsrc.begin(), lsrc.end());
-        auto dd1 = [&](double** p, size_t n) { return dalloc(h, (void**)p, n * sizeof(double)); };
-        if ((rc = dd1(&h->gobs, (size_t)Nl * kGO))) return fail(rc, "");
-        if ((rc = dd1(&h->Up, (size_t)C * 9))) return fail(rc, "");
-        if ((rc = dd1(&h->VY, (size_t)std::max(Pl, 1) * kVY))) return fail(rc, "");
-        if ((rc = dd1(&h->gpc, (size_t)C * 3))) return fail(rc, "");
-        if ((rc = dd1(&h->scl_cur, (size_t)std::max(Nl, 1)))) return fail(rc, "");
-        if ((rc = dd1(&h->scl_new, (size_t)std::max(Nl, 1)))) return fail(rc, "");
-        if ((rc = dd1(&h->ds, (size_t)std::max(Nl, 1)))) return fail(rc, "");
-    } else {
-        nivec<double> uvl((size_t)2 * Nl);
-        pool.ranges(Nl, [&](int, long long a, long long b) {
-            for (long long o = a; o < b; ++o) {
-                uvl[2 * (size_t)o] = obs[2 * (size_t)lsrc[o]];
-                uvl[2 * (size_t)o + 1] = obs[2 * (size_t)lsrc[o] + 1];
-            }
-        });
-        if ((rc = upload(h, &h->uv, uvl.data(), uvl.size()))) return fail(rc, "");
-        if ((rc = upload(h, &h->pp, cpar, (size_t)2 * C))) return fail(rc, "");
-    }
-    if ((rc = upload(h, &h->cam, lcam.data(), lcam.size()))) return fail(rc, "");
-    if ((rc = upload(h, &h->pt_ptr, lptr.data(), lptr.size()))) return fail(rc, "");
-    if ((rc = upload(h, &h->cam_ptr, cptr.data(), cptr.size()))) return fail(rc, "");
-    if ((rc = upload(h, &h->cam_obs, cobs.data(), cobs.size()))) return fail(rc, "");
-    // derived on the device from the four arrays above instead of uploaded (88 of 140 MB for config 3):
-    // per observation its track and the start of its upper partners; per camera-major entry the Schur descriptor and
-    // (BA) the linearization's point / uv gathers
-    if ((rc = dalloc(h, (void**)&h->ptl, sizeof(int) * (size_t)std::max(Nl, 1)))) return fail(rc, "");
-    if ((rc = dalloc(h, (void**)&h->ustart, sizeof(int) * (size_t)std::max(Nl, 1)))) return fail(rc, "");
-    if ((rc = dalloc(h, (void**)&h->sdesc, sizeof(int4) * (size_t)std::max(Nl, 1)))) return fail(rc, "");
-    if (kind != 1) {
-        if ((rc = dalloc(h, (void**)&h->cm_pt, sizeof(int) * (size_t)std::max(Nl, 1)))) return fail(rc, "");
-        if ((rc = dalloc(h, (void**)&h->cm_uv, sizeof(double) * 2 * (size_t)std::max(Nl, 1)))) return fail(rc, "");
-    }
-    if (Pl > 0) k_derive_tracks<<<cdiv(Pl, kThreads), kThreads, 0, h->stream>>>(Pl, h->pt_ptr, h->cam, h->ptl, h->ustart);
-    if (Nl > 0)
-        k_derive_cm<<<cdiv(Nl, kThreads), kThreads, 0, h->stream>>>(Nl, h->cam_obs, h->ptl, h->ustart, h->pt_ptr,
-                                                                    kind != 1 ? h->uv : nullptr, h->sdesc, h->cm_pt,
-                                                                    h->cm_uv);
-    if ((rc = launch_err(h, "k_derive"))) return fail(rc, "");
-    tick("uploads (observations)");
-    // The upper block pattern of S (row i: i, then the cameras j > i sharing a track) and the co-visibility graph (per
-    // camera every other camera sharing a track, weighted by the number of (obs of i, obs of j) pairs sharing one:
-    // the two-level clustering's weights).  Single rank: on the device (k_pattern, two passes), the lower half of the
-    // graph transposed from the upper on the host.  Multi-rank (every rank needs the global pattern, and holds only its
-    // shard's observations on the device) or INSFM_DIAG=pattern_host: one host pass over the global camera-major list.
-    std::vector<int> gcptr;
-    CovisGraph g;
-    std::vector<int> rptr(C + 1, 0), cols;
-    static const bool pattern_host = diag("pattern_host");
-    const bool gpu_pattern = !pattern_host && Pl == P && o0 == 0 && Nl == N && C <= kPatternMaxC && Nl > 0;
-    std::vector<int> upw;  // (device pattern) the pair count of every upper block, indexed like cols
-    if (gpu_pattern) {
-        gcptr = cptr;  // (single rank: the local camera-major list is the global one)
-        // (scratch from dalloc: a hipFree here would synchronize the device; it goes back with the handle's buffers)
-        int *dcnt = nullptr, *doff = nullptr, *dnb = nullptr, *dwt = nullptr;
-        const size_t lds = sizeof(int) * (size_t)C;
-        std::vector<int> ulen(C), uoff(C + 1, 0);
-        if ((rc = dalloc(h, (void**)&dcnt, sizeof(int) * (size_t)C))) return fail(rc, "");
-        if ((rc = dalloc(h, (void**)&doff, sizeof(int) * (size_t)(C + 1)))) return fail(rc, "");
-        hipError_t e = hipSuccess;
-        {
-            k_pattern<<<C, 256, lds, h->stream>>>(C, h->cam_ptr, h->cam_obs, h->ustart, h->ptl, h->pt_ptr, h->cam, dcnt,
-                                                  nullptr, nullptr, nullptr);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(ulen.data(), dcnt, sizeof(int) * (size_t)C, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        for (int i = 0; i < C && e == hipSuccess; ++i) uoff[i + 1] = uoff[i] + ulen[i];
-        const int U = uoff[C];
-        std::vector<int> unb(std::max(U, 1)), uwt(std::max(U, 1));
-        if (e == hipSuccess && ((rc = dalloc(h, (void**)&dnb, sizeof(int) * (size_t)std::max(U, 1))) ||
-                                (rc = dalloc(h, (void**)&dwt, sizeof(int) * (size_t)std::max(U, 1)))))
-            return fail(rc, "");
-        if (e == hipSuccess) e = hipMemcpyAsync(doff, uoff.data(), sizeof(int) * (size_t)(C + 1), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) {
-            k_pattern<<<C, 256, lds, h->stream>>>(C, h->cam_ptr, h->cam_obs, h->ustart, h->ptl, h->pt_ptr, h->cam, nullptr,
-                                                  doff, dnb, dwt);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && U > 0) e = hipMemcpyAsync(unb.data(), dnb, sizeof(int) * (size_t)U, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess && U > 0) e = hipMemcpyAsync(uwt.data(), dwt, sizeof(int) * (size_t)U, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return fail(INSFM_BA_EHIP, std::string("k_pattern: ") + hipGetErrorString(e));
-        for (int i = 0; i < C; ++i) rptr[i + 1] = rptr[i] + 1 + ulen[i];
-        cols.resize(rptr[C]);
-        upw.assign(rptr[C], 0);
-        for (int i = 0; i < C; ++i) {
-            cols[rptr[i]] = i;
-            for (int k = 0; k < ulen[i]; ++k) {
-                cols[rptr[i] + 1 + k] = unb[uoff[i] + k];
-                upw[rptr[i] + 1 + k] = uwt[uoff[i] + k];
-            }
-        }
-    } else {
-    nivec<int> gcpt;  // the point of every observation, camera-major (global)
-    pcount_sort(pool, N, C, nullptr, [&](int i) { return cam_idx[i]; }, gcpt, gcptr, [&](int i) { return pt_idx[i]; });
-    {
-        const int T = pool.size();
-        std::vector<std::vector<int>> pnb(T);
-        std::vector<std::vector<long long>> pw(T);
-        std::vector<int> nlen(C, 0), ulen(C, 0);
-        pool.ranges(C, [&](int t, long long i0, long long i1) {
-            std::vector<int> mark(C, -1), buf;
-            std::vector<long long> acc(C, 0);
-            for (int i = (int)i0; i < (int)i1; ++i) {
-                buf.clear();
-                for (int e = gcptr[i]; e < gcptr[i + 1]; ++e) {
-                    const int p = gcpt[e];
-                    for (int q = gptr[p]; q < gptr[p + 1]; ++q) {
-                        const int j = cam_idx[q];
-                        if (j == i) continue;  // (the observation itself and same-camera duplicates)
-                        if (mark[j] != i) { mark[j] = i; acc[j] = 0; buf.push_back(j); }
-                        acc[j] += 1;
-                    }
-                }
-                std::sort(buf.begin(), buf.end());
-                int up = 0;
-                for (int j : buf) { pnb[t].push_back(j); pw[t].push_back(acc[j]); up += j > i; }
-                nlen[i] = (int)buf.size();
-                ulen[i] = up;
-            }
-        });
-        g.ptr.assign(C + 1, 0);
-        for (int i = 0; i < C; ++i) {
-            g.ptr[i + 1] = g.ptr[i] + nlen[i];
-            rptr[i + 1] = rptr[i] + 1 + ulen[i];
-        }
-        g.nb.reserve(g.ptr[C]);
-        g.w.reserve(g.ptr[C]);
-        for (int t = 0; t < T; ++t) {
-            g.nb.insert(g.nb.end(), pnb[t].begin(), pnb[t].end());
-            g.w.insert(g.w.end(), pw[t].begin(), pw[t].end());
-        }
-        cols.resize(rptr[C]);
-        pool.ranges(C, [&](int, long long i0, long long i1) {
-            for (int i = (int)i0; i < (int)i1; ++i) {
-                int k = rptr[i];
-                cols[k++] = i;
-                for (int e = g.ptr[i]; e < g.ptr[i + 1]; ++e)
-                    if (g.nb[e] > i) cols[k++] = g.nb[e];
-            }
-        });
-    }
-    }
-    h->nnzb = rptr[C];
-    std::vector<int> brow(h->nnzb);
-    for (int i = 0; i < C; ++i)
-        for (int e = rptr[i]; e < rptr[i + 1]; ++e) brow[e] = i;
-    std::vector<int> lop(C + 1, 0);
-    for (int i = 0; i < C; ++i)
-        for (int e = rptr[i] + 1; e < rptr[i + 1]; ++e) lop[cols[e] + 1]++;
-    for (int c = 0; c < C; ++c) lop[c + 1] += lop[c];
-    std::vector<int> locol(std::max(1, lop[C])), loblk(std::max(1, lop[C]));
-    {
-        std::vector<int> fill(lop.begin(), lop.end() - 1);
-        for (int i = 0; i < C; ++i)
-            for (int e = rptr[i] + 1; e < rptr[i + 1]; ++e) {
-                const int k = fill[cols[e]]++;
-                locol[k] = i;
-                loblk[k] = e;
-            }
-    }
-    if (gpu_pattern) {  // the graph: per row the lower neighbours (transposed, ascending), then the upper ones
-        g.ptr.assign(C + 1, 0);
-        for (int i = 0; i < C; ++i) g.ptr[i + 1] = g.ptr[i] + (lop[i + 1] - lop[i]) + (rptr[i + 1] - rptr[i] - 1);
-        g.nb.resize(g.ptr[C]);
-        g.w.resize(g.ptr[C]);
-        for (int i = 0; i < C; ++i) {
-            int k = g.ptr[i];
-            for (int q = lop[i]; q < lop[i + 1]; ++q, ++k) { g.nb[k] = locol[q]; g.w[k] = upw[loblk[q]]; }
-            for (int e2 = rptr[i] + 1; e2 < rptr[i + 1]; ++e2, ++k) { g.nb[k] = cols[e2]; g.w[k] = upw[e2]; }
-        }
-    }
-    tick("block pattern + covisibility");
-    if (desc->precond < 0 || desc->precond > 2) return fail(INSFM_BA_EINVAL, "precond must be 0, 1 or 2");
-    // ---- two-level preconditioner: clusters ----
-    // Target cluster size 14 by default (config 3, same box, 3 x 3 runs: K = 16 / 14 / 12 -> 703-711 / 716-720 /
-    // 713-720 LM it/s, CG iterations per 10 steps 225 / 213 / 208; profiles/r3_v10/cluster_size_probe_*.log).
-    // While the coarse dimension exceeds kCoarseMax the target grows in proportion to the excess (at least by one),
-    // rounded up to even (aggregates below K / 2 are dissolved: an odd K would keep singletons):
-    // K' = max(K + 1, ceil(K nc MC / kCoarseMax)) rounded up to even, at most C -- the oracle's ora_cluster_cameras.
-    // With K = C the clusters are the co-visibility components: if even those do not fit (more components than
-    // kCoarseMax / MC), the solver runs the block-Jacobi PCG (precond 0) instead.
-    const int MC = D + 1;
-    int nc = 0;
-    bool coarse_ok = false;
-    std::vector<int>& lab = h->clab_host;
-    if (desc->precond >= 1 && h->d.optimize_poses) {
-        int K = std::min(desc->cluster_size > 0 ? desc->cluster_size : 24, C);
-        nc = aggregate(g, C, K, lab);
-        while (nc * MC > kCoarseMax && K < C) {
-            K = (int)std::min<long long>(C, std::max<long long>(K + 1, ((long long)K * nc * MC + kCoarseMax - 1) / kCoarseMax));
-            K += K & 1;
-            K = std::min(K, C);
-            nc = aggregate(g, C, K, lab);
-        }
-        coarse_ok = nc * MC <= kCoarseMax;
-    }
-    tick("clusters");
-    // flattened CG neighbour list per row: upper blocks then lower (transposed) ones -- with the two-level
-    // preconditioner each row's list is sorted by (cluster of the neighbour, neighbour), so that a row's
-    // neighbour-cluster segments are contiguous runs of its blocks (the register-resident CG kernel k_tl_cgp walks
-    // them in block order); pos_up/pos_lo give each upper
-    // block's two slots in the row-contiguous copy Sn
-    std::vector<int> nptr(C + 1, 0), nj, pup(std::max(1, h->nnzb), -1), plo(std::max(1, h->nnzb), -1);
-    nj.reserve(2 * (size_t)h->nnzb);
-    {
-        // per row entries (neighbour j, block e, 0 = upper slot / 1 = lower slot), in cluster order when the coarse
-        // space exists (stable: within a cluster the upper-then-lower order)
-        std::vector<int4> ent;
-        for (int i = 0; i < C; ++i) {
-            ent.clear();
-            for (int e = rptr[i] + 1; e < rptr[i + 1]; ++e) ent.push_back(make_int4(cols[e], e, 0, 0));
-            for (int k = lop[i]; k < lop[i + 1]; ++k) ent.push_back(make_int4(locol[k], loblk[k], 1, 0));
-            if (coarse_ok)
-                std::stable_sort(ent.begin(), ent.end(), [&](const int4& x, const int4& y) { return lab[x.x] < lab[y.x]; });
-            for (const int4& q : ent) {
-                (q.z ? plo : pup)[q.y] = (int)nj.size();
-                nj.push_back(q.x);
-            }
-            nptr[i + 1] = (int)nj.size();
-        }
-    }
-    // Equal-length rows (every row padded to the longest with zero blocks of neighbour = the row itself) when that
-    // costs at most 10 % more slots: the CG's product kernel then derives a row's range from its index instead of
-    // loading nbr_ptr first (one dependent memory round trip less per iteration).  The padded blocks stay zero (Sn is
-    // cleared at create and k_cg_scale never writes them), so every consumer of the lists may walk them unchanged.
-    {
-        int stride = 0;
-        for (int i = 0; i < C; ++i) stride = std::max(stride, nptr[i + 1] - nptr[i]);
-        const int64_t nn = (int64_t)nj.size();
-        if (stride > 0 && nn > 0 && (int64_t)C * stride * 10 <= nn * 11) {
-            // the pad slots of a row (neighbour = the row itself) go behind the row's own-cluster entries when the
-            // list is in cluster order, so that it stays in cluster order; else at the end
-            std::vector<int> nj2((size_t)C * stride), nptr2(C + 1), ins(C);
-            for (int i = 0; i < C; ++i) {
-                const int n = nptr[i + 1] - nptr[i], pad = stride - n;
-                int at = n;
-                if (coarse_ok) {
-                    at = 0;
-                    while (at < n && lab[nj[nptr[i] + at]] <= lab[i]) ++at;
-                }
-                ins[i] = at;
-                nptr2[i] = i * stride;
-                int* dst = nj2.data() + (size_t)i * stride;
-                for (int q = 0; q < n; ++q) dst[q < at ? q : q + pad] = nj[nptr[i] + q];
-                for (int q = 0; q < pad; ++q) dst[at + q] = i;
-            }
-            nptr2[C] = C * stride;
-            // remap the Sn slots of every upper block (row i = brow[e] for pos_up, row cols[e] for pos_lo)
-            auto slot = [&](int r, int p) {
-                const int q = p - nptr[r];
-                return r * stride + (q < ins[r] ? q : q + stride - (nptr[r + 1] - nptr[r]));
-            };
-            for (int e = 0; e < h->nnzb; ++e) {
-                if (e == rptr[brow[e]]) continue;  // diagonal block: no slot
-                const int i = brow[e], j = cols[e];
-                pup[e] = slot(i, pup[e]);
-                plo[e] = slot(j, plo[e]);
-            }
-            nj.swap(nj2);
-            nptr.swap(nptr2);
-            h->nbr_stride = stride;
-        }
-    }
-    h->n_nbr = (int64_t)nj.size();
-    for (int i = 0; i < C; ++i) { pup[rptr[i]] = 0; plo[rptr[i]] = 0; }  // diagonal blocks: unused slots
-    if (nj.empty()) nj.push_back(0);
-    tick("CG neighbour lists");
-    // Schur work items: split long rows so a chunk fits the LDS budget
-    // Deterministic mode's k_schur runs kDetWaves waves per workgroup taking their LDS adds in turn (round 6; one wave
-    // in round 5): its workgroups stage kDetWaves waves' W^ and take row chunks of <= kLdsTargetDet, so that three
-    // share a CU.  (With the 96-KB chunks of the 8-wave form one wave held a whole CU: k_schur 2.1 ms per trial on
-    // config 3 in deterministic mode.)
-    const bool det_schur = desc->deterministic != 0;
-    const size_t wsh_lds = sizeof(double) * (det_schur ? kDetWaves : kSchurWaves) * (64 / D) * schur_ws(D);  // W^ staging
-    const size_t fixed_lds = sizeof(double) * (D + 12) + sizeof(int) * (size_t)C + wsh_lds + 64;
-    if (fixed_lds + sizeof(double) * D * D > (size_t)kLdsBudget) return fail(INSFM_BA_EINVAL, "too many cameras for LDS");
-    // chunk target: kLdsTarget (deterministic mode kLdsTargetDet) when at least 8 blocks fit under it, else the hard
-    // budget
-    const size_t tgt0 = det_schur ? (size_t)kLdsTargetDet : (size_t)kLdsTarget;
-    const size_t tgt = tgt0 >= fixed_lds + 8 * sizeof(double) * schur_bs(D) ? tgt0 : (size_t)kLdsBudget;
-    const int cap = (int)((tgt - fixed_lds) / (sizeof(double) * schur_bs(D)));
-    std::vector<int4> work;
-    int maxc = 1;
-    for (int i = 0; i < C; ++i) {
-        if (gcptr[i + 1] == gcptr[i] && rptr[i + 1] - rptr[i] == 1) {
-            work.push_back(make_int4(i, rptr[i], rptr[i + 1], 0));
-            continue;
-        }
-        for (int kb = rptr[i]; kb < rptr[i + 1]; kb += cap) {
-            const int ke = std::min(kb + cap, rptr[i + 1]);
-            work.push_back(make_int4(i, kb, ke, 0));
-            maxc = std::max(maxc, ke - kb);
-        }
-    }
-    h->nwork = (int)work.size();
-    h->max_chunk = maxc;
-    if (kind == 0 && desc->allreduce_async && (desc->world_size > 1 || desc->allreduce) && desc->exchange_chunks > 1 &&
-        desc->optimize_poses) {
-        // chunk boundaries at rows splitting the blocks into about equal counts (geometric series of chunk sizes
-        // were measured in round 3 and do not pay: the all-reduces run back to back on one stream; DESIGN.md section
-        // 5), and the first work item of each boundary row
-        const int K = std::min(desc->exchange_chunks, C);
-        h->rptr_host = rptr;
-        h->xr.assign(1, 0);
-        h->xw.assign(1, 0);
-        for (int c = 1; c < K; ++c) {
-            const int64_t target = (int64_t)rptr[C] * c / K;
-            const int r = (int)(std::upper_bound(rptr.begin(), rptr.end(), (int)target) - rptr.begin()) - 1;
-            if (r <= h->xr.back() || r >= C) continue;
-            int w = h->xw.back();
-            while (w < (int)work.size() && work[w].x < r) ++w;
-            h->xr.push_back(r);
-            h->xw.push_back(w);
-        }
-        h->xr.push_back(C);
-        h->xw.push_back((int)work.size());
-        hipError_t e = hipStreamCreateWithFlags(&h->xstream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_x, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_xdone, hipEventDisableTiming);
-        if (e != hipSuccess) return fail(INSFM_BA_EHIP, std::string("exchange stream: ") + hipGetErrorString(e));
-    }
-    // Work order: natural (row order), so the 256 rows running at once are 256 consecutive cameras that share tracks
-    // in the Infinity Cache.
-    h->schur_lds = sizeof(double) * ((size_t)maxc * schur_bs(D) + D + 12) + wsh_lds + sizeof(int) * (size_t)C;
-    h->schur_lds = (h->schur_lds + 15) & ~(size_t)15;
-    // Camera linearization beside k_lin_points / k_schur (u_late), single rank (multi-rank, U / g_c are all-reduced
-    // before the Schur build adds them).
-    {
-        if (kind == 0 && desc->world_size <= 1 && !desc->allreduce) {
-            hipError_t e = helper_stream(1, 0, &h->aux);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_lin0, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_lc, hipEventDisableTiming);
-            if (e != hipSuccess) return fail(INSFM_BA_EHIP, std::string("linearization stream: ") + hipGetErrorString(e));
-            h->u_late = true;
-        }
-    }
-
-    if (kind != 1) {
-        std::vector<int> lb(1, 0);
-        for (int p = 0; p < Pl; ++p)  // close the run before a track that would overflow it
-            if (p > lb.back() && (lptr[p + 1] - lptr[lb.back()] > kLinThreads || p - lb.back() >= kLinThreads))
-                lb.push_back(p);
-        if (Pl > 0) lb.push_back(Pl);
-        h->n_lin = (int)lb.size() - 1;
-        if ((rc = upload(h, &h->lin_blk, lb.data(), lb.size()))) return fail(rc, "");
-    }
-    if ((rc = upload(h, &h->row_ptr, rptr.data(), rptr.size()))) return fail(rc, "");
-    if ((rc = upload(h, &h->col, cols.data(), cols.size()))) return fail(rc, "");
-    if ((rc = upload(h, &h->blk_row, brow.data(), brow.size()))) return fail(rc, "");
-    if ((rc = upload(h, &h->nbr_ptr, nptr.data(), nptr.size()))) return fail(rc, "");
-    if ((rc = upload(h, &h->nbr_j, nj.data(), nj.size()))) return fail(rc, "");
-    if ((rc = upload(h, &h->pos_up, pup.data(), pup.size()))) return fail(rc, "");
-    h->pos_up_host = pup;
-    if ((rc = upload(h, &h->pos_lo, plo.data(), plo.size()))) return fail(rc, "");
-    {
-        const int DPd = D + (D & 1);
-        const size_t snb = sizeof(double) * (size_t)std::max<int64_t>(h->n_nbr, 1) * D * DPd;
-        if ((rc = dalloc(h, (void**)&h->Sn, snb))) return fail(rc, "");
-        if (hipMemsetAsync(h->Sn, 0, snb, h->stream) != hipSuccess) return fail(INSFM_BA_EHIP, "Sn clear");
-    }
-    if ((rc = upload(h, &h->work, work.data(), work.size()))) return fail(rc, "");
-    auto dd = [&](double** p, size_t n) { return dalloc(h, (void**)p, n * sizeof(double)); };
-    // the CG's cross-workgroup hand-off buffers (atomic partial sums, exchanged w, tagged granules, barrier words) in
-    // uncached device memory (INSFM_DIAG=cgp_cached: ordinary memory, for A/B runs)
-    const bool uc = !diag("cgp_cached");
-    auto hand = [&](void** p, size_t bytes) { return dalloc(h, p, bytes, uc); };
-    // W: [3][D] records per observation (global positioning: its 32-B {u, beta^2} records fit in the same buffer)
-    if ((rc = dd(&h->W, (size_t)Nl * D * 3 + 2))) return fail(rc, "");
-    if ((rc = dd(&h->V, (size_t)Pl * 6))) return fail(rc, "");
-    if ((rc = dd(&h->gp, (size_t)Pl * 3))) return fail(rc, "");
-    if ((rc = dd(&h->Vinv, (size_t)Pl * 6))) return fail(rc, "");
-    if ((rc = dd(&h->y, (size_t)Pl * 3))) return fail(rc, "");
-    if (kind == 0) {
-        if ((rc = dd(&h->Rf, (size_t)Pl * 6))) return fail(rc, "");
-        if ((rc = dd(&h->Mp, (size_t)Pl * 6))) return fail(rc, "");
-    }
-    if ((rc = dd(&h->dp, (size_t)Pl * 3))) return fail(rc, "");
-    h->xcount = (int64_t)h->nnzb * D * D + (int64_t)C * D + (int64_t)C * D * D + (int64_t)C * D + 8;
-    if ((rc = dd(&h->xbuf, (size_t)h->xcount))) return fail(rc, "");
-    h->S = h->xbuf;
-    h->b = h->S + (size_t)h->nnzb * D * D;
-    h->U = h->b + (size_t)C * D;
-    h->gc = h->U + (size_t)C * D * D;
-    h->scal = h->gc + (size_t)C * D;
-    if ((rc = dd(&h->Lf, (size_t)C * D * D))) return fail(rc, "");
-    if ((rc = dd(&h->Li, (size_t)C * D * D))) return fail(rc, "");
-    if ((rc = dd(&h->dc, (size_t)C * D))) return fail(rc, "");
-    h->cg_nwg = C;  // one workgroup (and one partial record) per camera row
-    const size_t cd = (size_t)C * D;
-    const size_t cgn = 8 * cd + 2 * 3 * (size_t)h->cg_nwg + 2 * ((size_t)desc->pcg_max_iter + 2) + 16;
-    if ((rc = dd(&h->cgmem, cgn))) return fail(rc, "");
-    {
-        double* m = h->cgmem;
-        h->cg.r[0] = m; m += cd; h->cg.r[1] = m; m += cd;
-        h->cg.w[0] = m; m += cd; h->cg.w[1] = m; m += cd;
-        h->cg.s[0] = m; m += cd; h->cg.s[1] = m; m += cd;
-        h->cg.p = m; m += cd; h->cg.x = m; m += cd;
-        h->cg.part[0] = m; m += 3 * (size_t)h->cg_nwg; h->cg.part[1] = m; m += 3 * (size_t)h->cg_nwg;
-        h->cg.hist = m; m += 2 * ((size_t)desc->pcg_max_iter + 2);
-        h->cg.scal = m; m += 4;
-    }
-    if ((rc = dalloc(h, (void**)&h->cg.status, sizeof(int) * 4))) return fail(rc, "");
-    const int ST = h->stride;
-    if ((rc = dd(&h->cams_cur, (size_t)C * ST))) return fail(rc, "");
-    if ((rc = dd(&h->cams_new, (size_t)C * ST))) return fail(rc, "");
-    if ((rc = dd(&h->pts_cur, (size_t)std::max(Pl, 1) * 3))) return fail(rc, "");
-    if ((rc = dd(&h->pts_new, (size_t)std::max(Pl, 1) * 3))) return fail(rc, "");
-    h->n_cost = std::max(1, cdiv(Nl, kind == 1 ? kThreads : kCostThreads));
-    h->n_gp = std::max(1, cdiv(Pl, kThreads));
-    h->n_gp_grp = std::max(1, cdiv((long long)Pl * kGPG, kThreads));
-    if (kind == 1) h->n_gp = h->n_gp_grp;  // the gain partials of k_gp_backsub
-    else h->n_gp = std::max(1, h->n_lin);   // one per run of k_backsub
-    h->n_gc = std::max(1, cdiv(C, kLinThreads));  // camera-update blocks (ride along with k_backsub_rc)
-    if ((rc = dd(&h->part_cost, 2 * (size_t)h->n_cost))) return fail(rc, "");
-    if ((rc = dd(&h->part_gp, (size_t)h->n_gp))) return fail(rc, "");
-    if ((rc = dd(&h->part_gc, (size_t)h->n_gc))) return fail(rc, "");
-    h->result = h->scal;  // the 4 result scalars are all-reduced in place with the exchange buffer
-    if ((rc = dalloc(h, (void**)&h->flags, sizeof(int) * 4))) return fail(rc, "");
-    {
-        hipError_t e = hipHostMalloc((void**)&h->host_res, 128, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(INSFM_BA_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        // the published cost block (without it, or with a cross-rank sum installed, costs come back by copy + sync)
-        void* pm = nullptr;
-        if (hipHostMalloc(&pm, 16 * sizeof(double), hipHostMallocMapped) == hipSuccess) {
-            void* dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, pm, 0) == hipSuccess) {
-                h->pub_host = static_cast<double*>(pm);
-                h->pub_dev = static_cast<double*>(dp);
-                std::memset(pm, 0, 16 * sizeof(double));
-            } else {
-                (void)hipHostFree(pm);
-            }
-        }
-    }
-    for (auto& e : h->ev) {
-        hipError_t x = hipEventCreate(&e);
-        if (x != hipSuccess) return fail(INSFM_BA_EHIP, std::string("hipEventCreate: ") + hipGetErrorString(x));
-    }
-    if (desc->world_size > 1 || desc->allreduce) {
-        const hipError_t x = hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming);
-        if (x != hipSuccess) return fail(INSFM_BA_EHIP, std::string("hipEventCreate: ") + hipGetErrorString(x));
-    }
-    {
-        hipError_t e = hipMemsetAsync(h->part_gp, 0, sizeof(double) * h->n_gp, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(h->part_gc, 0, sizeof(double) * h->n_gc, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(h->flags, 0, sizeof(int) * 4, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return fail(INSFM_BA_EHIP, std::string("init: ") + hipGetErrorString(e));
-    }
-    // the Schur kernels may need more than the default dynamic-LDS limit
-    with_D(D, [&](auto dc_) -> int {
-        constexpr int DV = decltype(dc_)::value;
-        (void)hipFuncSetAttribute((const void*)k_schur<DV, kDetWaves, false, false, SCHUR_DET_ORD>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->schur_lds);
-        (void)hipFuncSetAttribute((const void*)k_schur<DV, kSchurWaves>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)h->schur_lds);
-        (void)hipFuncSetAttribute((const void*)k_schur<DV, kDetWaves, false, true, SCHUR_DET_ORD>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->schur_lds);
-        (void)hipFuncSetAttribute((const void*)k_schur<DV, kSchurWaves, false, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->schur_lds);
-        if constexpr (DV == 3) {
-            (void)hipFuncSetAttribute((const void*)k_schur<3, kDetWaves, true, false, SCHUR_DET_ORD>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->schur_lds);
-            (void)hipFuncSetAttribute((const void*)k_schur<3, kSchurWaves, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)h->schur_lds);
-            (void)hipFuncSetAttribute((const void*)k_schur_gp<kSchurWaves, kGPSG>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)h->schur_lds);
-        }
-        return 0;
-    });
-    tick("uploads + allocations");
-    if (coarse_ok) {
-        // ---- two-level preconditioner: source lists of E, buffers ----
-        const int m = nc * MC;
-        tick("covisibility + clusters");
-        std::vector<int> clp(nc + 1, 0), clc(C), alone(C);
-        for (int i = 0; i < C; ++i) clp[lab[i] + 1]++;
-        for (int c = 0; c < nc; ++c) clp[c + 1] += clp[c];
-        {
-            std::vector<int> fill(clp.begin(), clp.end() - 1);
-            for (int i = 0; i < C; ++i) clc[fill[lab[i]]++] = i;
-        }
-        int maxmem = 1;
-        for (int c = 0; c < nc; ++c) maxmem = std::max(maxmem, clp[c + 1] - clp[c]);
-        for (int i = 0; i < C; ++i) alone[i] = (clp[lab[i] + 1] - clp[lab[i]]) < 2;
-        // per row: neighbour slots ordered by (cluster of the neighbour, slot) and one segment per neighbour cluster
-        // (the row's own cluster always has one: it carries the diagonal term)
-        std::vector<int> sperm(std::max<int64_t>(h->n_nbr, 1), 0), rsp(C + 1, 0);
-        std::vector<int4> segs;
-        int maxseg = 1;
-        {
-            // rows in parallel (each row's segments into its own list), then concatenated in row order
-            std::vector<std::vector<int4>> rsegs(C);
-            pool.ranges(C, [&](int, long long i0, long long i1) {
-                std::vector<int> ord;
-                for (int i = (int)i0; i < (int)i1; ++i) {
-                    const int n0 = nptr[i], n1 = nptr[i + 1];
-                    ord.resize(n1 - n0);
-                    for (int q = 0; q < n1 - n0; ++q) ord[q] = n0 + q;
-                    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return lab[nj[x]] < lab[nj[y]]; });
-                    for (int q = 0; q < n1 - n0; ++q) sperm[n0 + q] = ord[q];
-                    const int own = lab[i];
-                    bool own_done = false;
-                    int q = 0;
-                    std::vector<int4>& out = rsegs[i];
-                    while (q < n1 - n0 || !own_done) {
-                        const int cq = q < n1 - n0 ? lab[nj[ord[q]]] : nc;
-                        if (!own_done && own < cq) {  // own cluster without neighbours in it
-                            out.push_back(make_int4(own, q, q, 1));
-                            own_done = true;
-                            continue;
-                        }
-                        int qe = q;
-                        while (qe < n1 - n0 && lab[nj[ord[qe]]] == cq) ++qe;
-                        out.push_back(make_int4(cq, q, qe, cq == own ? 1 : 0));
-                        if (cq == own) own_done = true;
-                        q = qe;
-                    }
-                }
-            });
-            for (int i = 0; i < C; ++i) {
-                segs.insert(segs.end(), rsegs[i].begin(), rsegs[i].end());
-                rsp[i + 1] = (int)segs.size();
-                maxseg = std::max(maxseg, (int)rsegs[i].size());
-            }
-        }
-        // E source lists per cluster pair (row cluster c', column cluster c): the segments of c's rows, rows ascending
-        std::vector<int> eptr((size_t)nc * nc + 1, 0), eseg;
-        eseg.reserve(segs.size());
-        {
-            std::vector<std::vector<int>> bucket(nc);
-            for (int cr = 0; cr < nc; ++cr) {
-                for (auto& v : bucket) v.clear();
-                for (int e = clp[cr]; e < clp[cr + 1]; ++e) {
-                    const int i = clc[e];
-                    for (int sidx = rsp[i]; sidx < rsp[i + 1]; ++sidx) bucket[segs[sidx].x].push_back(sidx);
-                }
-                for (int c = 0; c < nc; ++c) {
-                    eseg.insert(eseg.end(), bucket[c].begin(), bucket[c].end());
-                    eptr[(size_t)cr * nc + c + 1] = (int)eseg.size();
-                }
-            }
-        }
-        tick("coarse segments");
-        TlBufs& tl = h->tl;
-        tl.nc = nc;
-        tl.m = m;
-        tl.maxmem = maxmem;
-        const int ldE = gj_steps(m) * kGB;
-        tl.ldE = ldE;
-        int* ip = nullptr;
-        if ((rc = upload(h, &ip, clp.data(), clp.size()))) return fail(rc, "");
-        tl.cl_ptr = ip;
-        if ((rc = upload(h, &ip, clc.data(), clc.size()))) return fail(rc, "");
-        tl.cl_cams = ip;
-        {
-            std::vector<int> cpos(C);
-            for (int q = 0; q < C; ++q) cpos[clc[q]] = q;
-            if ((rc = upload(h, &ip, cpos.data(), cpos.size()))) return fail(rc, "");
-            tl.cpos = ip;
-        }
-        if ((rc = upload(h, &ip, alone.data(), alone.size()))) return fail(rc, "");
-        tl.alone = ip;
-        if ((rc = upload(h, &ip, sperm.data(), sperm.size()))) return fail(rc, "");
-        tl.sperm = ip;
-        if ((rc = upload(h, &ip, rsp.data(), rsp.size()))) return fail(rc, "");
-        tl.rseg_ptr = ip;
-        if ((rc = upload(h, &ip, eptr.data(), eptr.size()))) return fail(rc, "");
-        tl.ered_ptr = ip;
-        if (eseg.empty()) eseg.push_back(0);
-        if ((rc = upload(h, &ip, eseg.data(), eseg.size()))) return fail(rc, "");
-        tl.ered_seg = ip;
-        {
-            int4* sp = nullptr;
-            if ((rc = upload(h, &sp, segs.data(), segs.size()))) return fail(rc, "");
-            tl.seg = sp;
-        }
-        if ((rc = dd(&tl.u, cd))) return fail(rc, "");
-        if ((rc = dd(&tl.Zt, cd * MC))) return fail(rc, "");
-        if ((rc = dd(&tl.Ztc, cd * MC))) return fail(rc, "");
-        if ((rc = dd(&tl.vc, cd))) return fail(rc, "");
-        if ((rc = dd(&tl.Rc, (size_t)m))) return fail(rc, "");
-        if ((rc = dd(&tl.gd, 3 * (size_t)C))) return fail(rc, "");
-        {
-            if ((rc = upload(h, &ip, lab.data(), lab.size()))) return fail(rc, "");
-            tl.clab = ip;
-            // atomic cluster sums of the CG partials: single GPU, non-deterministic mode only -- the replicated
-            // multi-rank CG needs bitwise-equal inputs on every rank (config 3: CG iteration 23.9 -> 22.3 us, round 3)
-            tl.Racc = nullptr;
-            tl.Gacc = nullptr;
-            if (!desc->deterministic && desc->world_size <= 1 && !desc->allreduce) {
-                if ((rc = hand((void**)&tl.Racc, sizeof(double) * 3 * (size_t)m))) return fail(rc, "");
-                if ((rc = hand((void**)&tl.Gacc, sizeof(double) * 3 * 3 * (size_t)nc))) return fail(rc, "");
-                if (hipMemsetAsync(tl.Racc, 0, sizeof(double) * 3 * (size_t)m, h->stream) != hipSuccess ||
-                    hipMemsetAsync(tl.Gacc, 0, sizeof(double) * 9 * (size_t)nc, h->stream) != hipSuccess)
-                    return fail(INSFM_BA_EHIP, "Racc clear");
-            }
-        }
-        if ((rc = dd(&tl.rowR, (size_t)C * MC + 2))) return fail(rc, "");  // +2: k_tl_pc reads it in 16-B pairs
-        if ((rc = dd(&tl.Oseg, segs.size() * MC * MC))) return fail(rc, "");
-        {
-            // E is kept padded to whole blocks; the pad is the identity (k_tl_ereduce writes only the m x m part and
-            // the Gauss-Jordan steps keep the pad an identity)
-            std::vector<double> eye((size_t)ldE * ldE, 0.0);
-            for (int q = m; q < ldE; ++q) eye[(size_t)q * ldE + q] = 1.0;
-            for (int sl = 0; sl < 2; ++sl) {
-                if ((rc = upload(h, &h->Ebuf[sl], eye.data(), eye.size()))) return fail(rc, "");
-                if ((rc = dd(&h->Einvbuf[sl], (size_t)m * m))) return fail(rc, "");
-            }
-        }
-        if ((rc = dd(&h->gjW, (size_t)ldE * ldE))) return fail(rc, "");
-        if ((rc = dd(&h->gjP, (size_t)2 * kGB * kGB))) return fail(rc, "");
-        {
-            std::vector<double> ones(ldE, 1.0);   // equilibration of the pad (k_tl_ereduce writes the first m)
-            if ((rc = upload(h, &tl.Ed, ones.data(), ones.size()))) return fail(rc, "");
-        }
-        if ((rc = dalloc(h, (void**)&h->okbuf, sizeof(int) * 2))) return fail(rc, "");
-        tl.E = h->Ebuf[0];
-        tl.Einv = h->Einvbuf[0];
-        tl.ok = h->okbuf;
-        hipError_t e = hipMemsetAsync(h->okbuf, 0, sizeof(int) * 2, h->stream);
-        // The side stream (E build + factorization, off the critical path) at the lowest priority (ROCm exposes only
-        // normal and high: no measured effect either way, round 1)
-        int prio_lo = 0, prio_hi = 0;
-        if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        // (INSFM_DIAG=side_hi / side_normal: the side stream at the high / normal priority instead, for A/B runs)
-        const int side_prio = diag("side_hi") ? prio_hi : diag("side_normal") ? 0 : prio_lo;
-        if (e == hipSuccess) e = helper_stream(0, side_prio, &h->side);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_E, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_built, hipEventDisableTiming);
-        for (int sl = 0; sl < 2 && e == hipSuccess; ++sl) e = hipEventCreateWithFlags(&h->ev_fact[sl], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return fail(INSFM_BA_EHIP, std::string("two-level init: ") + hipGetErrorString(e));
-        h->erow_lds = 0;  // (k_tl_erow's LDS is static: a few KB)
-        (void)maxseg;
-        {
-            const size_t fixed = sizeof(double) * ((size_t)MC * m + (size_t)m), budget = 144 * 1024;
-            h->pc_rows = (int)std::min<size_t>((size_t)C, (budget - fixed) / (sizeof(double) * MC));
-            h->pc_lds = fixed + sizeof(double) * (size_t)h->pc_rows * MC;
-        }
-        if (h->erow_lds > 160 * 1024 || h->pc_lds > 150 * 1024)
-            return fail(INSFM_BA_EINVAL, "two-level preconditioner: scene too connected for the LDS budget (use precond 0)");
-        with_D(D, [&](auto dc_) -> int {
-            constexpr int DV = decltype(dc_)::value;
-            (void)hipFuncSetAttribute((const void*)k_tl_pc<DV>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)h->pc_lds);
-            return 0;
-        });
-        h->tlon = true;
-        void* pm = nullptr;
-        if (hipHostMalloc(&pm, sizeof(int) * 8, hipHostMallocMapped) == hipSuccess) {
-            h->prog_host = static_cast<int*>(pm);
-            void* dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, pm, 0) == hipSuccess) h->cg.prog = static_cast<int*>(dp);
-            else { (void)hipHostFree(pm); h->prog_host = nullptr; }
-        }
-        // the persistent register-resident CG (ba_cgp.h): D = 8, atomic cluster sums, host-mapped progress, rows of
-        // at most NB = 128 blocks in cluster order, at most kCgpSegMax neighbour clusters per row, and the whole grid
-        // resident at once
-        int maxlen = 0;
-        for (int i = 0; i < C; ++i) maxlen = std::max(maxlen, nptr[i + 1] - nptr[i]);
-        bool in_order = true;
-        for (int64_t q = 0; q < h->n_nbr && in_order; ++q) in_order = sperm[q] == q;
-        const int nb = (maxlen <= 64 && !diag("cgp128")) ? 64 : maxlen <= 128 ? 128 : 0;
-        const int grid = (C + kCgpRows - 1) / kCgpRows;
-        if (diag("create"))
-            std::fprintf(stderr, "[insfm create] k_tl_cgp eligibility: D %d, atomic sums %d, progress %d, max row %d, "
-                         "cluster order %d, max segments %d\n", D, tl.Racc != nullptr, h->prog_host != nullptr, maxlen,
-                         (int)in_order, maxseg);
-        // non-deterministic single rank: per-cluster atomic sums (tl.Racc); otherwise (deterministic mode, or every
-        // rank of a replicated multi-rank CG) the fixed-order variant
-        // (INSFM_DIAG=cgp_det: the fixed-order variant on a non-deterministic handle too, for A/B runs)
-        const bool det = tl.Racc == nullptr || diag("cgp_det");
-        // precond 2 (A-DEF2) in either form (round 6: the fixed-order DET form too); the launch path runs the additive
-        // form of precond 1
-        const bool adef = desc->precond == 2;
-        if (D == 8 && h->prog_host && nb && in_order && maxseg <= kCgpSegMax && !diag("no_cgp")) {
-            int dev = 0, ncu = 0, per_cu = 0;
-            hipError_t ce = hipGetDevice(&dev);
-            if (ce == hipSuccess) ce = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-            if (ce == hipSuccess)
-                ce = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)cgp_kernel(nb, det, adef), kCgpThreads,
-                                                                  0);
-            if (ce == hipSuccess && per_cu >= 1 && grid <= ncu) {
-                if ((rc = hand((void**)&h->cgp_wx, sizeof(double) * 2 * cd))) return fail(rc, "");
-                if ((rc = hand((void**)&h->cgp_yg, sizeof(unsigned long long) * 2 * kCoarseMax))) return fail(rc, "");
-                if (hipMemsetAsync(h->cgp_yg, 0, sizeof(unsigned long long) * 2 * kCoarseMax, h->stream) != hipSuccess)
-                    return fail(INSFM_BA_EHIP, "cgp granules");
-                if ((rc = hand((void**)&h->cgp_sync, sizeof(unsigned) * kCgpSyncWords))) return fail(rc, "");
-                if (hipMemsetAsync(h->cgp_sync, 0, sizeof(unsigned) * kCgpSyncWords, h->stream) != hipSuccess)
-                    return fail(INSFM_BA_EHIP, "cgp barrier words");
-                if (diag("cgp_trace") && (rc = dd(&h->cgp_trace, kCgpTraceLen))) return fail(rc, "");
-                // the run records: DET's partials by parity, and (every form) the restriction of r0 that
-                // k_cg_factor_basis writes for the setup
-                if ((rc = hand((void**)&h->cgp_runs, sizeof(double) * 2 * 12 * (size_t)grid * kCgpRows)))
-                    return fail(rc, "");
-                // k_tl_cgp holds S unscaled: the S block (and orientation) of every slot, and the unscaled basis
-                {
-                    std::vector<int> src((size_t)std::max<int64_t>(h->n_nbr, 1), kCgpPadSlot);
-                    for (int e = 0; e < h->nnzb; ++e) {
-                        if (e == rptr[brow[e]]) continue;  // diagonal block: no slot
-                        src[pup[e]] = e;
-                        src[plo[e]] = ~e;
-                    }
-                    if ((rc = upload(h, &h->cgp_src, src.data(), src.size()))) return fail(rc, "");
-                    if ((rc = dd(&tl.Gb, cd * MC))) return fail(rc, "");
-                }
-                h->cgp_det = det;
-                h->adef2 = adef;
-                h->cgp_nb = nb;
-                h->cgp_grid = grid;
-                h->cgp_slots = per_cu * ncu;
-                if (diag("create"))
-                    std::fprintf(stderr, "[insfm create] k_tl_cgp<%d>: %d workgroups, %d CUs, %d per CU\n", nb, grid, ncu,
-                                 per_cu);
-            }
-        }
-    }
-    tick("two-level setup (end)");
-    if (kind == 0 && diag("stamps")) {
-        const size_t n = (size_t)kStampSteps * kStKinds * 2;
-        if ((rc = dalloc(h, (void**)&h->stamps, sizeof(long long) * n))) return fail(rc, "");
-        if (hipMemsetAsync(h->stamps, 0, sizeof(long long) * n, h->stream) != hipSuccess) return fail(INSFM_BA_EHIP, "stamps");
-    }
-    h->damping = 1.0 / desc->tr_radius;
-    h->down = desc->tr_down;
-    *out = h;
-    return INSFM_BA_OK;
-}
-
-}  // namespace
+#include "ba_create.h"
 
 extern "C" {
 

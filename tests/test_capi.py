@@ -12,10 +12,10 @@ from instantsfm_amd import _capi
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header_functions():
+def header_functions(only=None):
     names = set()
     for h in sorted(os.listdir(os.path.join(REPO, "include"))):
-        if h.endswith(".h"):
+        if h.endswith(".h") and (only is None or h in only):
             txt = open(os.path.join(REPO, "include", h)).read()
             txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
             names |= set(re.findall(r"\b(insfm_[a-z_]+)\s*\(", txt))
@@ -34,6 +34,20 @@ def test_library_exports_every_header_symbol():
     for name in header_functions():
         assert hasattr(L, name), name
     assert set(header_functions()) == set(_capi.SYMBOLS)
+
+
+def test_product_header_is_free_of_debug_entry_points():
+    """insfm_ba.h is the product ABI; introspection, timing probes and the partitioned-CG prototype live in
+    insfm_ba_debug.h."""
+    assert set(_capi.SYMBOLS) == set(_capi.PUBLIC_SYMBOLS) | set(_capi.DEBUG_SYMBOLS)
+    assert not set(_capi.PUBLIC_SYMBOLS) & set(_capi.DEBUG_SYMBOLS)
+    other = set(header_functions(only=("insfm_passes.h", "insfm_tracks.h")))  # (their own headers, same library)
+    ba = {n for n in _capi.PUBLIC_SYMBOLS if not n.startswith("insfm_gp_")} - other
+    assert set(header_functions(only=("insfm_ba.h",))) == ba
+    assert "debug" not in open(os.path.join(REPO, "include", "insfm_ba.h")).read()
+    assert set(header_functions(only=("insfm_ba_debug.h",))) == set(_capi.DEBUG_SYMBOLS)
+    public = set(header_functions(only=("insfm_ba.h", "insfm_gp.h", "insfm_passes.h", "insfm_tracks.h")))
+    assert public == set(_capi.PUBLIC_SYMBOLS)
 
 
 def test_struct_layout_matches_header():
