@@ -1614,1193 +1614,8 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 // ============================================================================================================
 #include "ba_handle.h"
 
-namespace {
-
-int allreduce(insfm_ba* h, double* buf, int64_t n) {
-    // a single rank skips the exchange unless a callback is installed (tests drive the RCCL path with one rank)
-    if (h->d.world_size <= 1 && !h->d.allreduce) return 0;
-    if (!h->d.allreduce) { h->err = "world_size > 1 needs an allreduce callback"; return INSFM_BA_ECOMM; }
-    int rc = h->d.allreduce(h->d.allreduce_ctx, buf, n);
-    if (rc) { h->err = "allreduce callback failed (" + std::to_string(rc) + ")"; return INSFM_BA_ECOMM; }
-    return 0;
-}
-
-int allreduce_async(insfm_ba* h, double* buf, int64_t n) {
-    int rc = h->d.allreduce_async(h->d.allreduce_ctx, buf, n, h->xstream);
-    if (rc) { h->err = "allreduce_async callback failed (" + std::to_string(rc) + ")"; return INSFM_BA_ECOMM; }
-    return 0;
-}
-
-long long* stamp_ptr(const insfm_ba* h, int kind) {
-    if (!h->stamps) return nullptr;
-    return h->stamps + ((size_t)(h->stamp_step % kStampSteps) * kStKinds + kind) * 2;
-}
-
-void rec(insfm_ba* h, int k) {
-    if (h->timing) (void)hipEventRecord(h->ev[k], h->stream);
-}
-
-// INSFM_DIAG=trace2: host timestamps of one LM step's API calls (labels + microseconds since the step began),
-// printed to stderr when the step ends -- where the host, not the GPU, sets the pace
-bool host_trace2() {
-    static const bool v = diag("trace2");
-    return v;
-}
-void hmark(insfm_ba* h, const char* what) {
-    if (host_trace2()) h->hmarks.emplace_back(what, wall_seconds());
-}
-
-// after a stream sync: add the device time between events a and b to phase `slot`
-void acc_time(insfm_ba* h, int a, int b, int slot) {
-    if (!h->timing) return;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev[a], h->ev[b]) == hipSuccess) h->tms[slot] += ms;
-}
-
-// ---- phases --------------------------------------------------------------------------------------------------
-// The main stream waits for the camera linearization on `aux` (before anything reads U / g_c).
-int lin_join(insfm_ba* h) {
-    if (!h->lin_pending) return 0;
-    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_lc, 0));
-    h->lin_pending = false;
-    return 0;
-}
-
-// The first trial's point preparation of a BA linearization (PointPrep): damping factor f = 1 + damping, records Y
-// (and R_p) only when the poses are optimized (points-only solves have no Schur complement).
-PointPrep first_trial_prep(insfm_ba* h) {
-    PointPrep pp1;
-    pp1.f = 1.0 + h->damping;
-    pp1.cmin = h->d.clamp_min;
-    pp1.cmax = h->d.clamp_max;
-    pp1.Vinv = h->Vinv;
-    pp1.y = h->y;
-    pp1.R = h->d.optimize_poses ? h->Rf : nullptr;
-    pp1.flags = h->flags;
-    pp1.status = h->cg.status;
-    return pp1;
-}
-
-template <int M>
-void launch_lin_points_w(insfm_ba* h, const double* cams, const double* pts_local, const PointPrep& pp1) {
-    k_lin_points<M><<<h->n_lin, kLinThreads, 0, h->stream>>>(h->lin_blk, h->pt_ptr, h->cam, h->ptl, h->uv, h->pp, cams,
-                                                         pts_local, h->d.huber_delta, pp1.R ? h->W : nullptr, h->V, h->gp,
-                                                         pp1, stamp_ptr(h, kStLinPoints));
-}
-
-int run_linearize(insfm_ba* h, const double* cams, const double* pts_local) {
-    h->tl_fresh = true;
-    if (h->kind == 1) {
-        if (h->Nl > 0)
-            k_gp_lin<<<cdiv(h->Nl, kThreads), kThreads, 0, h->stream>>>(h->Nl, h->cam, h->ptl, h->trans, h->fcam, h->sfree,
-                                                                       cams, pts_local, h->scl_cur, h->d.huber_delta, h->gobs);
-        k_gp_lin_cams<<<h->C, kThreads, 0, h->stream>>>(h->C, h->cam_ptr, h->cam_obs, h->gobs, h->U, h->gc);
-        int rc = launch_err(h, "k_gp_lin");
-        if (rc) return rc;
-        return allreduce(h, h->U, (int64_t)h->C * h->D * h->D + (int64_t)h->C * h->D);
-    }
-    if (int rc0 = lin_join(h)) return rc0;  // (the previous linearization's U / g_c writes come first)
-    // The first trial's point preparation rides along with k_lin_points (PointPrep): lm_step's first trial runs at
-    // f = 1 + damping (config 3, same box, 3 runs each: 725 / 722 / 701 -> 733 / 725 / 734 LM it/s against a separate
-    // k_point_prep launch; profiles/r3_v13/prep_fuse_ab.log).  The records Y_o depend on it (R_p).
-    const PointPrep pp1 = first_trial_prep(h);
-    h->prep_valid = false;
-    if (h->kind == 0 && h->Pl > 0) {
-        if (h->flags_dirty) {  // a solve without a cost left the flags / status set: clear them first (k_zero_words)
-            k_zero_words<<<1, 64, 0, h->stream>>>(h->flags, h->cg.status);
-            if (int e = launch_err(h, "k_zero_words")) return e;
-            h->flags_dirty = false;
-        }
-        h->prep_valid = true;
-        h->prep_f = pp1.f;
-    }
-    hipStream_t cst = h->aux;
-    int rc = with_model(h->model, [&](auto mc) -> int {
-        constexpr int M = decltype(mc)::value;
-        constexpr int D = kD<M>;
-        // k_lin_cams (compute-bound) forks after k_lin_points (HBM-bound) so that it overlaps k_schur (bound by
-        // gather latency) instead of competing with k_lin_points for bandwidth
-        if (h->u_late && h->Pl > 0) launch_lin_points_w<M>(h, cams, pts_local, pp1);
-        if (h->u_late) {
-            HIPCHK(hipEventRecord(h->ev_lin0, h->stream));
-            HIPCHK(hipStreamWaitEvent(h->aux, h->ev_lin0, 0));
-            if constexpr (D <= 9) {
-                k_lin_cams_reg<M><<<h->C, LIN_CAMS_NT, 0, cst>>>(h->cam_ptr, h->cm_pt, h->cm_uv, h->pp, cams, pts_local,
-                                                              h->d.huber_delta, h->U, h->gc);
-            } else {
-                const size_t lds = sizeof(double) * kThreads * (2 * D + 2);
-                k_lin_cams<M><<<h->C, kThreads, lds, cst>>>(h->cam_ptr, h->cm_pt, h->cm_uv, h->pp, cams, pts_local,
-                                                            h->d.huber_delta, h->U, h->gc);
-            }
-            if (int e = launch_err(h, "k_lin_cams")) return e;
-            HIPCHK(hipEventRecord(h->ev_lc, h->aux));
-            h->lin_pending = true;
-            return launch_err(h, "k_lin_points");
-        }
-        if (h->Pl > 0) launch_lin_points_w<M>(h, cams, pts_local, pp1);
-        if constexpr (D <= 9) {
-            k_lin_cams_reg<M><<<h->C, LIN_CAMS_NT, 0, h->stream>>>(h->cam_ptr, h->cm_pt, h->cm_uv, h->pp, cams,
-                                                                pts_local, h->d.huber_delta, h->U, h->gc);
-            return launch_err(h, "linearize");
-        }
-        const size_t lds = sizeof(double) * kThreads * (2 * D + 2);
-        k_lin_cams<M><<<h->C, kThreads, lds, h->stream>>>(h->cam_ptr, h->cm_pt, h->cm_uv, h->pp, cams, pts_local,
-                                                          h->d.huber_delta, h->U, h->gc);
-        return launch_err(h, "linearize");
-    });
-    if (rc) return rc;
-    return allreduce(h, h->U, (int64_t)h->C * h->D * h->D + (int64_t)h->C * h->D);
-}
-
-// Two-level setup, part 1: coarse basis Z~ (on `basis_stream`, the CG needs it) and E into slot `slot` (on
-// `build_stream`, which must already be ordered after the basis).
-int run_tl_basis(insfm_ba* h, const double* cams, hipStream_t stream) {
-    const int C = h->C;
-    if (h->kind == 1) {
-        k_tl_basis<kGP><<<h->tl.nc, kThreads, 0, stream>>>(C, cams, h->Lf, h->tl, h->cg.r[0]);
-        return launch_err(h, "k_tl_basis");
-    }
-    return with_model(h->model, [&](auto mc) -> int {
-        constexpr int M = decltype(mc)::value;
-        constexpr int MC = kD<M> + 1;
-        k_tl_basis<M><<<h->tl.nc, kThreads, 0, stream>>>(C, cams, h->Lf, h->tl, h->cg.r[0], stamp_ptr(h, kStBasis));
-        (void)MC;
-        return launch_err(h, "k_tl_basis");
-    });
-}
-
-// The side stream's E build runs with at most kErowGrid workgroups (rows strided over the grid): with one workgroup
-// per row it held CU / LDS slots the overlapping CG launches needed (config 3, round 1: grid 1000 / 512 / 384 / 256 /
-// 192 / 128 -> 593 / 616 / 612-615 / 603 / 594 LM it/s).
-constexpr int kErowGrid = 256;
-int run_tl_build(insfm_ba* h, int slot, hipStream_t stream, bool have_oseg = false) {
-    const int C = h->C, m = h->tl.m;
-    TlBufs tl = h->tl;
-    tl.E = h->Ebuf[slot];
-    return with_D(h->D, [&](auto dc_) -> int {
-        constexpr int DV = decltype(dc_)::value;
-        const int grid = stream != h->stream ? std::min(C, kErowGrid) : C;
-        if (!have_oseg)  // (k_tl_cgp wrote the segments of this solve)
-            k_tl_erow<DV><<<grid, kThreads, 0, stream>>>(C, h->nbr_ptr, h->nbr_j, h->Sn, tl);
-        k_tl_ereduce<DV><<<cdiv(m * m, kThreads), kThreads, 0, stream>>>(tl);
-        return launch_err(h, "k_tl_erow/ereduce");
-    });
-}
-
-// Two-level setup, part 2: unit u of E_slot's Gauss-Jordan inversion on `stream` (launch_gj_unit; the last writes
-// Einvbuf[slot]).
-int run_tl_gj_unit(insfm_ba* h, int slot, int u, hipStream_t stream) {
-    launch_gj_unit(u, h->tl.m, h->Ebuf[slot], h->gjW, h->gjP, h->tl.Ed, h->Einvbuf[slot], h->okbuf + slot, stream);
-    return launch_err(h, "k_gj_pinv0/k_gj_step");
-}
-
-// Per solve (after k_cg_factor / k_cg_scale on the main stream): the basis Z~ on the main stream, then E_n's build
-// (reads S~ and Z~) and factorization on the side stream.  The CG is pointed at the coarse inverse of the previous
-// solve when this is the first solve after a linearization (it starts right away), otherwise at its own (it waits
-// for the factorization) -- the oracle's lag rule (ora_pcg).  The next solve's k_cg_scale / k_tl_basis overwrite
-// S~ / Z~, so they wait for ev_built (run_solve).
-// CG iterations the host keeps queued ahead of the device: 1 since late round 3 (config 3, same box, 3 runs each:
-// 2 / 1 / 0 -> 714-721 / 722-726 / 720-727 LM it/s; every queued iteration a converged CG still runs costs ~9 us;
-// profiles/r3_v12/cg_ahead_ab.log)
-#ifndef CG_AHEAD
-#define CG_AHEAD 1
-#endif
-#ifndef CG_INIT_BACK
-#define CG_INIT_BACK 2
-#endif
-constexpr int kCgAhead = CG_AHEAD;
-
-// The side-stream chain of solve `slot`: wait for the basis (ev_E), the E build (k_tl_erow, k_tl_ereduce), ev_built,
-// then the Gauss-Jordan launches, the last followed by ev_fact[slot].  The whole chain (~20 launches) is issued at the
-// solve's setup, while the GPU is still in k_lin_points / k_schur: the host is then ~0.6 ms ahead of the GPU, the
-// launches cost the GPU nothing, and the chain overlaps the CG.  (Round 2 issued it piecemeal from the CG poll loop,
-// and a chain deferred past the CG was measured too: both slower)
-// set_timing: the device time of finished side chains (start after the wait on ev_E, end after the last Gauss-Jordan
-// unit) into phase slot 6 of the current step.  A chain issued behind the CG usually finishes during the next step, so
-// it is counted there; summed over the steps of a run every chain is counted once (but the last one).
-void harvest_chain_time(insfm_ba* h) {
-    for (int sl = 0; sl < 2; ++sl) {
-        if (!h->chain_timed[sl] || hipEventQuery(h->ev[14 + sl]) != hipSuccess) continue;
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, h->ev[12 + sl], h->ev[14 + sl]) == hipSuccess) h->tms[6] += ms;
-        h->chain_timed[sl] = false;
-    }
-}
-
-int issue_side_chain(insfm_ba* h, int slot, bool have_oseg = false) {
-    hipStream_t fs = h->side;
-    HIPCHK(hipStreamWaitEvent(fs, h->ev_E, 0));
-    const bool tm = h->timing && !h->chain_timed[slot];
-    if (tm) HIPCHK(hipEventRecord(h->ev[12 + slot], fs));
-    if (int rc = run_tl_build(h, slot, fs, have_oseg)) return rc;
-    h->chain_oseg = have_oseg;
-    HIPCHK(hipEventRecord(h->ev_built, fs));
-    h->built_pending = true;
-    for (int u = 0; u <= gj_steps(h->tl.m); ++u)
-        if (int rc = run_tl_gj_unit(h, slot, u, fs)) return rc;
-    HIPCHK(hipEventRecord(h->ev_fact[slot], fs));
-    if (tm) {
-        HIPCHK(hipEventRecord(h->ev[14 + slot], fs));
-        h->chain_timed[slot] = true;
-    }
-    return 0;
-}
-
-// Everything of the side chain finished (debug getters, kernel timing, destroy, reset).
-int side_flush(insfm_ba* h) {
-    if (h->side) HIPCHK(hipStreamSynchronize(h->side));
-    return 0;
-}
-
-// Per-solve setup on the main stream: the basis, then this solve's side chain; the CG uses the previous solve's
-// E^-1 under the lag rule, else its own (the main stream waits for the factorization).
-int run_tl_setup(insfm_ba* h, const double* cams) {
-    const int slot = (int)(h->tl_solves & 1);
-    if (h->timing) harvest_chain_time(h);
-    int rc = h->basis_by_factor ? 0 : run_tl_basis(h, cams, h->stream);  // (k_cg_factor_basis formed it)
-    if (rc) return rc;
-    const int use = (h->tl_solves > 0 && h->tl_fresh) ? (slot ^ 1) : slot;
-    h->tl_fresh = false;
-    // k_tl_cgp under the lag rule: this solve's chain runs after the CG (run_tl_cg records ev_E behind the CG; an
-    // event record here as well would only cost the main queue a marker); else it runs now and the CG waits
-    h->cgp_defer = h->cgp_nb && use != slot;
-    h->cgp_slot = slot;
-    if (!h->cgp_defer) {
-        HIPCHK(hipEventRecord(h->ev_E, h->stream));
-        if ((rc = issue_side_chain(h, slot))) return rc;
-    }
-    // a lagged solve's coarse inverse normally finished long ago: a completed event needs no wait marker in the main
-    // queue (each one idles it a few us; always queueing it measured 659-665 vs 659-664 LM it/s, round 2)
-    if (use == slot || hipEventQuery(h->ev_fact[use]) != hipSuccess)
-        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_fact[use], 0));
-    h->tl.Einv = h->Einvbuf[use];
-    h->tl.ok = h->okbuf + use;
-    ++h->tl_solves;
-    return 0;
-}
-
-// Launch `it` of the two-level CG: update (recurrence step it-1 when it >= 1; restriction always), coarse
-// correction, S~ u.
-template <int D>
-void launch_tl_iter(insfm_ba* h, int it, int maxit, double tol2) {
-    if (it == 0) {  // setup: restriction of r0, u0 = M~^-1 r0, w0 = S~ u0 and the partials of iteration 0
-        // (the restriction of r0 was formed by k_tl_basis)
-        k_tl_pc<D><<<h->tl.nc, kPcThreads, h->pc_lds, h->stream>>>(-1, h->C, maxit, tol2, h->pc_rows, h->cg, h->tl,
-                                                                   h->tl.Einv);
-        k_tl_pspmv<D><<<h->C, kPspmvThreads, 0, h->stream>>>(-1, h->C, h->nbr_stride, h->nbr_ptr, h->nbr_j, h->Sn, h->Lf,
-                                                              h->cg, h->tl, XPart{});
-    }
-    if (h->tl.Racc)  // per-cluster atomic sums of the row partials (single rank, non-deterministic)
-        k_tl_pc_cl<D><<<h->tl.nc, kPcThreads, 0, h->stream>>>(it, h->C, maxit, tol2, h->cg, h->tl, h->tl.Einv);
-    else
-        k_tl_pc<D><<<h->tl.nc, kPcThreads, h->pc_lds, h->stream>>>(it, h->C, maxit, tol2, h->pc_rows, h->cg, h->tl,
-                                                                   h->tl.Einv);
-    k_tl_pspmv<D><<<h->C, kPspmvThreads, 0, h->stream>>>(it, h->C, h->nbr_stride, h->nbr_ptr, h->nbr_j, h->Sn, h->Lf,
-                                                          h->cg, h->tl, XPart{});
-}
-
-// TlBufs whose exchanged buffers (vc, gd, rowR) are window region q of a partitioned handle
-TlBufs tl_region(const insfm_ba* h, int q) {
-    TlBufs t = h->tl;
-    const int C = h->C, D = h->D, MC = D + 1;
-    double* base = h->xwin + h->xoff_region[q];
-    t.vc = base;
-    t.gd = base + (size_t)C * D;
-    t.rowR = base + (size_t)C * D + 3 * (size_t)C;
-    (void)MC;
-    return t;
-}
-
-XPart xpart_region(const insfm_ba* h, int q) {
-    XPart xp;
-    xp.win = h->xbases;
-    xp.world = h->d.world_size;
-    xp.q0 = h->xq[h->d.rank];
-    xp.off_vc = h->xoff_region[q];
-    xp.off_gd = xp.off_vc + (long long)h->C * h->D;
-    xp.off_rowR = xp.off_gd + 3LL * h->C;
-    return xp;
-}
-
-// One exchange of the partitioned CG (slot 0: iterations, skipped once the CG status is set; 1: solution gather)
-void launch_xchg(insfm_ba* h, int slot) {
-    k_xsignal<<<1, 64, 0, h->stream>>>(h->cg.status, h->xcnt, h->xpflags, h->d.world_size, h->d.rank, slot);
-    k_xwait<<<1, 64, 0, h->stream>>>(h->cg.status, h->cg.prog, h->xcnt,
-                                     reinterpret_cast<unsigned*>(h->xwin + h->xoff_flags), h->d.world_size, slot);
-}
-
-// launch_tl_iter for a row-partitioned handle: k_tl_pc replicated on region it & 1, this rank's rows of k_tl_pspmv
-// writing region (it + 1) & 1 of every window, then the exchange
-template <int D>
-void launch_tl_iter_x(insfm_ba* h, int it, int maxit, double tol2) {
-    const int nrows = h->xq[h->d.rank + 1] - h->xq[h->d.rank];
-    auto pspmv = [&](int i) {
-        if (nrows > 0)
-            k_tl_pspmv<D><<<nrows, kPspmvThreads, 0, h->stream>>>(i, h->C, h->nbr_stride, h->nbr_ptr, h->nbr_j, h->Sn,
-                                                                  h->Lf, h->cg, tl_region(h, i & 1),
-                                                                  xpart_region(h, (i + 1) & 1));
-        launch_xchg(h, 0);
-    };
-    if (it == 0) {  // setup (k_tl_basis wrote r0 and its restriction into region 1)
-        k_tl_pc<D><<<h->tl.nc, kPcThreads, h->pc_lds, h->stream>>>(-1, h->C, maxit, tol2, h->pc_rows, h->cg,
-                                                                   tl_region(h, 1), h->tl.Einv);
-        pspmv(-1);
-    }
-    k_tl_pc<D><<<h->tl.nc, kPcThreads, h->pc_lds, h->stream>>>(it, h->C, maxit, tol2, h->pc_rows, h->cg,
-                                                               tl_region(h, it & 1), h->tl.Einv);
-    pspmv(it);
-}
-
-// The k_tl_cgp instantiation for NB blocks per row (64 / 128), the fixed-order form (det) and A-DEF2 (adef).
-using CgpKernel = void (*)(int, const int*, const int*, const double*, const int*, const double*, const double*, CgBufs,
-                           TlBufs, const double*, int, double, double*, unsigned long long*, unsigned, unsigned*, unsigned,
-                           int, double*, double*, double*, long long*);
-CgpKernel cgp_kernel(int nb, bool det, bool adef) {
-    if (nb == 64) {
-        if (det) return adef ? k_tl_cgp<64, true, true> : k_tl_cgp<64, true, false>;
-        return adef ? k_tl_cgp<64, false, true> : k_tl_cgp<64, false, false>;
-    }
-    if (det) return adef ? k_tl_cgp<128, true, true> : k_tl_cgp<128, true, false>;
-    return adef ? k_tl_cgp<128, false, true> : k_tl_cgp<128, false, false>;
-}
-
-// The whole two-level CG of a solve on the persistent k_tl_cgp (D = 8, h->cgp_nb > 0): one launch for the coarse
-// solve of r0 (u0 = M~^-1 r0, formerly k_tl_pc's setup launch), the setup's operator product and every iteration.
-int launch_tl_cgp(insfm_ba* h, int maxit, double tol2) {
-    if (h->cgp_epochs > (1u << 24)) {  // (counter headroom: zero them now and then; an abort zeroes them too)
-        HIPCHK(hipMemsetAsync(h->cgp_sync, 0, sizeof(unsigned) * kCgpSyncWords, h->stream));
-        h->cgp_epochs = 0;
-    }
-    // INSFM_DIAG=cgp_fault (tests): the first launch of the process aborts at iteration 2
-    static std::atomic<int> faults{diag("cgp_fault") ? 1 : 0};
-    const bool fault = faults.load() > 0 && faults.fetch_sub(1) > 0;
-    // INSFM_DIAG=adef2_breakdown (tests): the first A-DEF2 launch of the process reports a breakdown at iteration 2
-    static std::atomic<int> bkdn{diag("adef2_breakdown") ? 1 : 0};
-    const bool breakdown = h->adef2 && bkdn.load() > 0 && bkdn.fetch_sub(1) > 0;
-    hipLaunchKernelGGL(cgp_kernel(h->cgp_nb, h->cgp_det, h->adef2), dim3(h->cgp_grid), dim3(kCgpThreads), 0, h->stream,
-                       h->C, h->nbr_ptr, h->nbr_j, (const double*)h->S, (const int*)h->cgp_src, (const double*)h->Li,
-                       (const double*)h->Lf, h->cg, h->tl, (const double*)h->tl.Einv, maxit, tol2, h->cgp_wx, h->cgp_yg,
-                       h->cgp_tag, h->cgp_sync, h->cgp_epochs,
-                       (h->cgp_defer ? 1 : 0) | (fault ? 2 : 0) | (breakdown ? 4 : 0) | (h->basis_by_factor ? 0 : 8),
-                       h->cgp_runs, h->cgp_trace, h->dc,
-                       stamp_ptr(h, kStCgp));
-    return launch_err(h, "k_tl_cgp");
-}
-
-// k_schur for the handle's kind (BA: template on D; global positioning: D = 3 with the compact W record).
-int launch_schur(insfm_ba* h, const double* Uin, const double* gcin, double sf, double smin, double smax, int sdiag,
-                 bool retry, int w0 = 0, int w1 = -1) {
-    const bool det = h->d.deterministic != 0;
-    if (w1 < 0) w1 = h->nwork;
-    const int nt = det ? kDetWaves * 64 : kSchurWaves * 64;
-    if (h->kind == 1) {
-        if (det)
-            k_schur<3, kDetWaves, true, false, SCHUR_DET_ORD><<<h->nwork, nt, h->schur_lds, h->stream>>>(
-                h->work, h->row_ptr, h->col, h->C, h->cam_ptr, h->cam_obs, h->ptl, h->pt_ptr, h->ustart, h->sdesc, h->cam, h->W,
-                h->Vinv, h->y, Uin, gcin, sf, smin, smax, sdiag, h->S, h->b, nullptr);
-        else
-            k_schur_gp<kSchurWaves, kGPSG><<<h->nwork, nt, h->schur_lds, h->stream>>>(
-                h->work, h->row_ptr, h->col, h->C, h->cam_ptr, h->sdesc, h->cam, h->W, h->VY, Uin, gcin, h->S, h->b);
-        return launch_err(h, "k_schur");
-    }
-    return with_D(h->D, [&](auto dc_) -> int {
-        constexpr int DV = decltype(dc_)::value;
-        if (w1 <= w0) return 0;
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(w1 - w0), dim3(nt), h->schur_lds, h->stream,
-                h->work + w0, h->row_ptr, h->col, h->C, h->cam_ptr, h->cam_obs, h->ptl, h->pt_ptr, h->ustart, h->sdesc, h->cam,
-                h->W, h->Mp, h->y, Uin, gcin, sf, smin, smax, sdiag, h->S, h->b, stamp_ptr(h, kStSchur));
-        };
-        if (det) retry ? go(k_schur<DV, kDetWaves, false, true, SCHUR_DET_ORD>) : go(k_schur<DV, kDetWaves, false, false, SCHUR_DET_ORD>);
-        else retry ? go(k_schur<DV, kSchurWaves, false, true>) : go(k_schur<DV, kSchurWaves>);
-        return launch_err(h, "k_schur");
-    });
-}
-
-// The k_tl_cgp launch of this solve has finished (the host saw its status word, or the trial's k_publish behind
-// it): its status {status, iterations, coarse used} into st, the barrier bookkeeping, an abort's fallback, the trace.
-int cgp_complete(insfm_ba* h, int* st) {
-    std::atomic_thread_fence(std::memory_order_seq_cst);
-    volatile int* pg = h->prog_host;
-    st[0] = pg[1]; st[1] = pg[2]; st[2] = pg[3];
-    {  // the barriers this launch counted: one per completed iteration; an abort restarts the counters
-        if (st[0] == 1 || st[0] == 2) {
-            // (the setup's two barriers and one per completed iteration; A-DEF2: three and two)
-            h->cgp_epochs += h->adef2 ? 2u * (unsigned)st[1] + 3u : (unsigned)st[1] + 2u;
-        } else {
-            HIPCHK(hipStreamSynchronize(h->stream));
-            HIPCHK(hipMemsetAsync(h->cgp_sync, 0, sizeof(unsigned) * kCgpSyncWords, h->stream));
-            h->cgp_epochs = 0;
-            // a barrier timed out: the grid was not resident at once (another process's kernels held CUs).  A single
-            // rank drops the persistent CG for good and run_solve repeats this solve on the launch path; a rank of a
-            // replicated multi-rank CG cannot (its peers would compute a dc that differs in rounding) and reports it.
-            if (st[0] == 4 && h->d.world_size <= 1 && !h->xpart) {
-                std::fprintf(stderr, "[insfm] k_tl_cgp: a grid barrier timed out (the GPU is shared with another "
-                                     "process?); this handle continues on the launch-per-iteration CG\n");
-                h->cgp_nb = 0;
-                h->cgp_lost = true;
-            }
-        }
-    }
-    if (h->cgp_trace) {
-        double tr[kCgpTraceLen];
-        HIPCHK(hipMemcpy(tr, h->cgp_trace, sizeof(tr), hipMemcpyDeviceToHost));
-        const int n = std::min(st[1], 63);
-        std::fprintf(stderr, "[insfm cgp] status %d iterations %d coarse %d: setup %.1f us (blocks + tables %.1f, A %.1f, "
-                     "rest %.1f), iterations %.1f us (%.2f us each)\n",
-                     st[0], st[1], st[2], 0.01 * (tr[257] - tr[256]), 0.01 * (tr[578] - tr[256]),
-                     0.01 * (tr[579] - tr[578]), 0.01 * (tr[257] - tr[579]), 0.01 * (tr[258 + n] - tr[257]),
-                     n > 0 ? 0.01 * (tr[258 + n] - tr[258]) / n : 0.0);
-        for (int k = 0; k <= n; ++k) {
-            std::fprintf(stderr, "[insfm cgp]   it %d gamma %.17g delta %.17g rho %.17g done %g t %.1f us | loads %.2f P1 %.2f y %.2f "
-                         "P2 %.2f B2 %.2f\n", k, tr[4 * k], tr[4 * k + 1], tr[4 * k + 2], tr[4 * k + 3], 0.01 * (tr[258 + k] - tr[256]),
-                         k > 0 ? 0.01 * (tr[258 + k] - tr[322 + 4 * (k - 1) + 3]) : 0.0,
-                         0.01 * (tr[322 + 4 * k] - tr[258 + k]), 0.01 * (tr[323 + 4 * k] - tr[322 + 4 * k]),
-                         0.01 * (tr[324 + 4 * k] - tr[323 + 4 * k]), 0.01 * (tr[325 + 4 * k] - tr[324 + 4 * k]));
-            if (k < n)
-                std::fprintf(stderr, "[insfm cgp]        P1 split: fills + workgroup barrier %.2f, y %.2f, S~w %.2f; "
-                             "scalar partials in %.2f after the barrier\n",
-                             0.01 * (tr[580 + 3 * k] - tr[258 + k]), 0.01 * (tr[581 + 3 * k] - tr[580 + 3 * k]),
-                             0.01 * (tr[322 + 4 * k] - tr[581 + 3 * k]),
-                             k > 0 ? 0.01 * (tr[582 + 3 * k] - tr[322 + 4 * (k - 1) + 3]) : 0.0);
-        }
-        const int G = std::min(h->cgp_grid, 256);
-        if (st[1] > kCgpTraceIt + 1 && G > 0) {  // every workgroup's start and end of iteration kCgpTraceIt
-            double s0 = tr[772], s1 = tr[772];
-            for (int b = 0; b < G; ++b) { s0 = std::min(s0, tr[772 + b]); s1 = std::max(s1, tr[772 + b]); }
-            std::vector<int> ord(G);
-            for (int b = 0; b < G; ++b) ord[b] = b;
-            std::sort(ord.begin(), ord.end(), [&](int a, int b) { return tr[1028 + a] > tr[1028 + b]; });
-            std::fprintf(stderr, "[insfm cgp] it %d per workgroup: starts within %.2f us; arrival at the barrier "
-                         "(us after the first start): median %.2f, last %.2f; latest:", kCgpTraceIt, 0.01 * (s1 - s0),
-                         0.01 * (tr[1028 + ord[G / 2]] - s0), 0.01 * (tr[1028 + ord[0]] - s0));
-            for (int q = 0; q < std::min(G, 8); ++q)
-                std::fprintf(stderr, " wg %d (%.2f, start %.2f)", ord[q], 0.01 * (tr[1028 + ord[q]] - s0),
-                             0.01 * (tr[772 + ord[q]] - s0));
-            std::fprintf(stderr, "\n");
-        }
-    }
-    return 0;
-}
-
-
-// The two-level CG (precond 1): iterations enqueued from a host poll loop, no stream sync inside the CG.  k_tl_pc's
-// lead workgroup publishes its progress into host-mapped memory; more iterations are enqueued while the GPU has fewer
-// than kCgAhead pending, and the loop ends when the status word turns non-zero.  The few iterations enqueued past
-// convergence exit at the device status flag.  Returns 0 with st[0..2] = {status, iterations, coarse used}.
-int run_tl_cg(insfm_ba* h, int* st) {
-    const int D = h->D, maxit = h->d.pcg_max_iter;
-    h->dc_by_cgp = h->cgp_nb != 0;
-    const double tol2 = h->d.pcg_tol * h->d.pcg_tol;
-    volatile int* pg = h->prog_host;
-    pg[0] = pg[1] = pg[2] = pg[3] = 0;
-    std::atomic_thread_fence(std::memory_order_seq_cst);
-    // INSFM_DIAG=trace: per solve, host microseconds spent enqueueing CG iterations and the longest single call
-    static const bool htrace = diag("trace");
-    double t_enq = 0.0, m_enq = 0.0, t_sol0 = htrace ? wall_seconds() : 0.0;
-    int n_enq = 0;
-    auto enqueue = [&](int from, int to) -> int {
-        const double t0 = htrace ? wall_seconds() : 0.0;
-        if (h->cgp_nb) return from == 0 ? launch_tl_cgp(h, maxit, tol2) : 0;
-        const int r = with_D(D, [&](auto dc_) -> int {
-            constexpr int DV = decltype(dc_)::value;
-            for (int k = from; k < to; ++k) {
-                if (h->xpart) launch_tl_iter_x<DV>(h, k, maxit, tol2);
-                else launch_tl_iter<DV>(h, k, maxit, tol2);
-            }
-            return launch_err(h, "k_tl_pc/k_tl_pspmv");
-        });
-        if (htrace) { const double dt = wall_seconds() - t0; t_enq += dt; m_enq = std::max(m_enq, dt / std::max(1, to - from)); n_enq += to - from; }
-        return r;
-    };
-    rec(h, 8);
-    // multi-rank: the CG's first launch waits for the exchange (the slowest peer); the stall deadline starts once
-    // everything queued in front of the CG has completed (ev_pre), and that gate has its own longer deadline
-    const bool gated = h->d.world_size > 1 || h->d.allreduce;
-    if (gated) HIPCHK(hipEventRecord(h->ev_pre, h->stream));
-    // first batch: a little less than the last solve's count (counts drift by a few iterations per LM step); the loop
-    // below tops up one iteration at a time
-    int enq = std::min(std::max(kCgAhead + 2, h->last_cg_iters - CG_INIT_BACK), maxit + 2);
-    if (h->cgp_nb) enq = maxit + 2;  // k_tl_cgp: one launch runs every iteration
-    if (int rc = enqueue(0, enq)) return rc;
-    if (h->cgp_nb) h->cgp_tag += (unsigned)maxit + 3u;  // (the tags of this launch are never reused)
-    if (h->cgp_defer) {  // the side chain of this solve behind the CG (run_tl_setup), from k_tl_cgp's segments
-        // (INSFM_DIAG=chain_hold, timing only: no lagged chain at all -- later solves keep an older coarse inverse --
-        // to measure what the chain's overlap costs the kernels it runs beside)
-        static const bool hold = diag("chain_hold");
-        if (!hold) {
-            HIPCHK(hipEventRecord(h->ev_E, h->stream));
-            if (int rc = issue_side_chain(h, h->cgp_slot, true)) return rc;
-        } else {
-            h->chain_oseg = false;
-        }
-        h->cgp_defer = false;
-    }
-    if (h->cgp_nb && h->cg_async) {
-        // one launch runs the whole CG and the kernels behind it need no host decision: the host queues them at once
-        // and reads the CG status after the trial's k_publish (cgp_complete), which accepts the trial only for a
-        // converged CG.  (Waiting here for the status word cost a host round trip and a launch from an idle queue
-        // between the CG and k_cg_finish.)
-        rec(h, 9);
-        h->cg_launches += 1;
-        h->cgp_pending = true;
-        st[0] = 1; st[1] = 0; st[2] = 1;
-        return 0;
-    }
-    CgPoll poll;
-    poll.enq = enq;
-    static const double stall_s = cg_stall_limit_s(std::getenv("INSFM_CG_STALL_S"));
-    int erc = 0;
-    const int pr = cg_poll(
-        poll, maxit + 2, kCgAhead, stall_s, cg_gate_limit_s(stall_s), [&] { return (int)pg[1]; },
-        [&] { return (int)pg[0]; }, enqueue,
-        [&] {
-            const hipError_t q = hipStreamQuery(h->stream);
-            if (q == hipSuccess) { std::atomic_thread_fence(std::memory_order_seq_cst); return 0; }
-            return q == hipErrorNotReady ? 1 : -1;
-        },
-        wall_seconds,
-        [] {
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        },
-        [&] { return !gated || hipEventQuery(h->ev_pre) != hipErrorNotReady; }, &erc);
-    hmark(h, "cg converged");
-    if (htrace)
-        std::fprintf(stderr, "[insfm host] solve %.1f us: %d iterations enqueued in %.1f us (max %.1f per iteration)\n",
-                     1e6 * (wall_seconds() - t_sol0), n_enq, 1e6 * t_enq, 1e6 * m_enq);
-    enq = poll.enq;
-    if (pr == CgPoll::kEnqueueError) return erc;
-    if (pr == CgPoll::kStreamError) {
-        h->err = std::string("PCG: ") + hipGetErrorString(hipStreamQuery(h->stream));
-        return INSFM_BA_EHIP;
-    }
-    if (pr == CgPoll::kStalled || pr == CgPoll::kGateStalled) {
-        h->err = std::string(pr == CgPoll::kGateStalled ? "PCG: the cross-rank exchange in front of the CG did not "
-                                                          "complete within "
-                                                        : "PCG: no progress from the device for ") +
-                 std::to_string(poll.stalled_s) + " s (iterations started " + std::to_string(pg[0]) + ", status " +
-                 std::to_string(pg[1]) + ", enqueued " + std::to_string(enq) +
-                 "); set INSFM_CG_STALL_S to change the limit";
-        return INSFM_BA_EHIP;
-    }
-    std::atomic_thread_fence(std::memory_order_seq_cst);
-    rec(h, 9);
-    if (h->timing) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        acc_time(h, 8, 9, 5);
-    }
-    h->cg_launches += h->cgp_nb ? 1 : enq;
-    if (h->cgp_nb) return cgp_complete(h, st);
-    st[0] = pg[1]; st[1] = pg[2]; st[2] = pg[3];
-    return 0;
-}
-
-// The block-Jacobi CG (precond 0, or the two-level path without host-mapped memory): launches in chunks, a status
-// copy and a stream sync per chunk.
-int run_bj_cg(insfm_ba* h, int* st) {
-    const int D = h->D, maxit = h->d.pcg_max_iter;
-    const double tol2 = h->d.pcg_tol * h->d.pcg_tol;
-    int it = 0;
-    for (;;) {
-        // the count grows by a few iterations per LM step as the damping drops: launch past the last count so most
-        // solves need one host poll (a converged iteration costs ~1 us per launch: its kernels exit at the flag)
-        const int chunk = (it == 0) ? std::max(8, h->last_cg_iters + 6) : 8;
-        const int stop = std::min(it + chunk, maxit + 2);
-        const int first = it;
-        rec(h, 8);
-        const int rc = with_D(D, [&](auto dc_) -> int {
-            constexpr int DV = decltype(dc_)::value;
-            for (int k = it; k < stop; ++k) {
-                if (h->tlon) {
-                    if (h->xpart) launch_tl_iter_x<DV>(h, k, maxit, tol2);
-                    else launch_tl_iter<DV>(h, k, maxit, tol2);
-                    continue;
-                }
-                if (k > 0) k_cg_dots<<<1, 64, 0, h->stream>>>(k, h->C, maxit, tol2, h->cg);
-                k_cg_iter<DV><<<h->C, kCgThreads, 0, h->stream>>>(k, h->C, maxit, tol2, h->nbr_ptr, h->nbr_j, h->Sn,
-                                                                h->Lf, h->cg);
-            }
-            return launch_err(h, "k_cg_iter");
-        });
-        if (rc) return rc;
-        rec(h, 9);
-        it = stop;
-        HIPCHK(hipMemcpyAsync(st, h->cg.status, sizeof(int) * 3, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        acc_time(h, 8, 9, 5);
-        h->cg_launches += stop - first;
-        if (st[0] != 0 || it >= maxit + 2) break;
-    }
-    return 0;
-}
-
-// Build S/b for factor f, solve, back-substitute and form the trial parameters.  Returns PCG iterations (>= 0),
-// INSFM_BA_ESOLVER on breakdown, or another negative code.
-// After the CG of a solve: its status (breakdown -> ESOLVER), the partitioned CG's solution gather, dc = L^-T x.
-// Returns the PCG iterations (0 while a k_tl_cgp status is still pending) or an error.
-int cg_tail(insfm_ba* h, int* st) {
-    const int D = h->D;
-    int rc = 0;
-    if (st[0] != 1) {
-        h->err = std::string("PCG ") +
-                 (st[0] == 2 ? "breakdown"
-                  : st[0] == 4 ? "timed out (a k_tl_cgp grid barrier or a cross-rank exchange of the partitioned CG)"
-                               : "did not finish") +
-                 " at iteration " +
-                 std::to_string(st[1]) + " (status " + std::to_string(st[0]) + ", coarse " +
-                 (h->tlon ? std::to_string(st[2]) : std::string("off")) + ")";
-        return st[0] == 4 ? INSFM_BA_EHIP : INSFM_BA_ESOLVER;
-    }
-    if (!h->cgp_pending) {
-        h->coarse_used = h->tlon ? st[2] : 0;
-        h->last_cg_iters = st[1];
-    }
-    if (h->xpart) {  // partitioned CG: every rank's solution rows into every window, then into cg.x
-        const int n = h->xq[h->d.rank + 1] - h->xq[h->d.rank];
-        if (n > 0)
-            k_xput_x<<<cdiv((long long)n * D, 256), 256, 0, h->stream>>>(n, D, h->tl.cl_cams, h->cg.x,
-                                                                        xpart_region(h, 0), h->xoff_xg);
-        launch_xchg(h, 1);
-        HIPCHK(hipMemcpyAsync(h->cg.x, h->xwin + h->xoff_xg, sizeof(double) * (size_t)h->C * D,
-                              hipMemcpyDeviceToDevice, h->stream));
-        if ((rc = launch_err(h, "partitioned CG gather"))) return rc;
-        int sw[2] = {0, 0};  // (prototype path: one synchronization to see a gather that timed out)
-        HIPCHK(hipMemcpyAsync(sw, h->cg.status, sizeof(sw), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (sw[0] == 4) {
-            h->err = "partitioned CG: the solution gather across ranks timed out";
-            return INSFM_BA_EHIP;
-        }
-    }
-    if (h->dc_by_cgp) return h->cgp_pending ? 0 : st[1];  // (k_tl_cgp wrote dc; an abort's launch-path repeat clears it)
-    rc = with_D(D, [&](auto dc_) -> int {
-        constexpr int DV = decltype(dc_)::value;
-        k_cg_finish<DV><<<cdiv((long long)h->C * DV, kThreads), kThreads, 0, h->stream>>>(h->C, h->Li, h->cg.x,
-                                                                                        h->dc, stamp_ptr(h, kStCgFinish));
-        return launch_err(h, "k_cg_finish");
-    });
-    if (rc) return rc;
-    hmark(h, "cg_finish");
-    return h->cgp_pending ? 0 : st[1];
-}
-
-int solve_tail(insfm_ba* h, double f, const double* cams, const double* pts_local, const double* dcp);
-
-// The scaled copy Sn of the current solve's S~ (k_cg_scale), for consumers that read it when the solve skipped it
-// (k_tl_cgp's lagged solves): the launch-path CG after an abort, the debug timing of launch-path kernels.
-int ensure_sn(insfm_ba* h) {
-    if (h->sn_valid || h->kind != 0 || !h->d.optimize_poses) return 0;
-    const int rc = with_D(h->D, [&](auto dc_) -> int {
-        constexpr int DV = decltype(dc_)::value;
-        k_cg_scale<DV><<<cdiv(h->nnzb, kWaves * scale_nb(DV)), kThreads, 0, h->stream>>>(
-            h->nnzb, h->blk_row, h->col, h->row_ptr, h->pos_up, h->pos_lo, h->Li, h->S, h->Sn, 0);
-        return launch_err(h, "k_cg_scale");
-    });
-    if (!rc) h->sn_valid = true;
-    return rc;
-}
-
-// After a k_tl_cgp abort: the basis was formed again on the main stream; a side chain issued from the launch's coarse
-// segments (incomplete when a workgroup never got past the A build) is issued once more from S~ / Z~ (k_tl_erow),
-// behind the first on the side stream, so the next solve's coarse inverse is this solve's.
-int reissue_chain(insfm_ba* h) {
-    if (!h->chain_oseg) return 0;
-    h->chain_oseg = false;
-    HIPCHK(hipEventRecord(h->ev_E, h->stream));
-    return issue_side_chain(h, h->cgp_slot);
-}
-
-int run_solve(insfm_ba* h, double f, const double* cams, const double* pts_local) {
-    const int D = h->D;
-    // the point preparation of the linearization covers this solve when it runs at the prepared damping factor
-    const bool prepared = h->prep_valid && h->prep_f == f && h->kind == 0;
-    h->prep_valid = false;
-    // The non-PD flag is cleared by the k_final that consumed it and the CG status word by k_point_prep; one tiny
-    // launch clears both only when that chain is broken (a solve not followed by a cost, or no local points).
-    if (h->flags_dirty || h->Pl == 0 || h->kind == 1) {
-        k_zero_words<<<1, 64, 0, h->stream>>>(h->flags, h->cg.status);
-        const int rc0 = launch_err(h, "k_zero_words");
-        if (rc0) return rc0;
-    }
-    h->flags_dirty = true;
-    const bool gpk = h->kind == 1;
-    // global positioning: the scale-eliminated blocks are already damped, so k_schur takes U'/g'_c as they are
-    const double* Uin = gpk ? h->Up : h->U;
-    const double* gcin = gpk ? h->gpc : h->gc;
-    const double sf = gpk ? 1.0 : f;
-    const double smin = gpk ? -1.0e308 : h->d.clamp_min, smax = gpk ? 1.0e308 : h->d.clamp_max;
-    const int sdiag = gpk ? 1 : (h->u_late ? 0 : (h->d.rank == 0));  // u_late: U / g_c added by k_cg_factor
-    if (gpk) {
-        if (h->Pl > 0)
-            k_gp_prep_points<kGPG><<<cdiv((long long)h->Pl * kGPG, kThreads), kThreads, 0, h->stream>>>(h->Pl, h->pt_ptr, h->gobs, f, h->d.clamp_min,
-                                                                               h->d.clamp_max, h->W, h->V, h->gp, h->Vinv,
-                                                                               h->y, h->VY, h->flags);
-        k_gp_prep_cams<<<h->C, kThreads, 0, h->stream>>>(h->C, h->cam_ptr, h->cam_obs, h->gobs, h->U, h->gc, f,
-                                                                     h->d.clamp_min, h->d.clamp_max, h->d.rank == 0, h->Up,
-                                                                     h->gpc);
-    } else if (h->Pl > 0 && !prepared && (hmark(h, "point_prep"), true))
-        k_point_prep<<<cdiv(h->Pl, kThreads), kThreads, 0, h->stream>>>(h->Pl, h->V, h->gp, f, h->d.clamp_min, h->d.clamp_max,
-                                                                       h->Vinv, h->y, h->flags, h->cg.status,
-                                                                       h->d.optimize_poses ? h->Rf : nullptr, h->Mp);
-    int iters = 0;
-    const double* dcp = nullptr;
-    if (h->d.optimize_poses) {
-        rec(h, 6);
-        int rc = 0;
-        if (h->xstream) {
-            // chunked exchange: each row chunk's blocks of S are summed across ranks on the exchange stream while the
-            // next chunk's Schur rows are built; b (filled by every row) after the last chunk
-            const int K = (int)h->xw.size() - 1;
-            for (int c = 0; c < K; ++c) {
-                if ((rc = launch_schur(h, Uin, gcin, sf, smin, smax, sdiag, !prepared, h->xw[c], h->xw[c + 1]))) return rc;
-                const int64_t b0 = h->rptr_host[h->xr[c]], b1 = h->rptr_host[h->xr[c + 1]];
-                HIPCHK(hipEventRecord(h->ev_x, h->stream));
-                HIPCHK(hipStreamWaitEvent(h->xstream, h->ev_x, 0));
-                // set_timing: the exchange's span on its stream, from the first chunk's start to b's end (phase 7)
-                if (h->timing && c == 0) HIPCHK(hipEventRecord(h->ev[16], h->xstream));
-                if (b1 > b0 && (rc = allreduce_async(h, h->S + b0 * D * D, (b1 - b0) * D * D))) return rc;
-            }
-            if ((rc = allreduce_async(h, h->b, (int64_t)h->C * D))) return rc;
-            HIPCHK(hipEventRecord(h->ev_xdone, h->xstream));
-            if (h->timing) HIPCHK(hipEventRecord(h->ev[17], h->xstream));
-            HIPCHK(hipStreamWaitEvent(h->stream, h->ev_xdone, 0));
-            rec(h, 7);
-        } else {
-            rc = launch_schur(h, Uin, gcin, sf, smin, smax, sdiag, !prepared);
-            if (rc) return rc;
-            hmark(h, "schur");
-            rec(h, 7);
-            rc = allreduce(h, h->S, (int64_t)h->nnzb * D * D + (int64_t)h->C * D);
-            if (rc) return rc;
-        }
-        if (h->built_pending) {  // the side stream's E build of the previous solve still reads S~ / Z~
-            HIPCHK(hipStreamWaitEvent(h->stream, h->ev_built, 0));
-            h->built_pending = false;
-        }
-        if ((rc = lin_join(h))) return rc;
-        const bool ul = h->u_late && !gpk;
-        // k_tl_cgp holds S unscaled and scales the vectors (ba_cgp.h): a lagged solve on it (whose E build behind
-        // the CG takes the coarse segments k_tl_cgp writes) needs no scaled copy Sn; the first solve after a
-        // linearization that factorizes its own E (k_tl_erow reads Sn), the launch-path CG and the debug getters do
-        const bool scale = !(h->tlon && h->cgp_nb && h->tl_solves > 0 && h->tl_fresh && !h->keep_S);
-        // the persistent CG's solves: the factorization and the coarse basis in one launch (k_cg_factor_basis)
-        h->basis_by_factor = FACTOR_BASIS && h->tlon && h->cgp_nb && !gpk;
-        rc = with_D(D, [&](auto dc_) -> int {
-            constexpr int DV = decltype(dc_)::value;
-            if constexpr (DV != 3) {
-                if (h->basis_by_factor) {
-                    k_cg_factor_basis<DV><<<cdiv(h->C, kWaves), kThreads, 0, h->stream>>>(
-                        h->C, h->row_ptr, h->S, h->b, h->Lf, h->Li, h->cg, ul ? h->U : nullptr, ul ? h->gc : nullptr,
-                        f, h->d.clamp_min, h->d.clamp_max, cams, h->tl, h->cgp_runs + (size_t)h->cgp_grid * kCgpRows * 12,
-                        stamp_ptr(h, kStFactor));
-                }
-            }
-            if (!h->basis_by_factor)
-                k_cg_factor<DV><<<cdiv(h->C, kWaves), kThreads, 0, h->stream>>>(
-                    h->C, h->row_ptr, h->S, h->b, h->Lf, h->Li, h->cg, ul ? h->U : nullptr, ul ? h->gc : nullptr, f,
-                    h->d.clamp_min, h->d.clamp_max, stamp_ptr(h, kStFactor));
-            if (scale)
-                k_cg_scale<DV><<<cdiv(h->nnzb, kWaves * scale_nb(DV)), kThreads, 0, h->stream>>>(
-                    h->nnzb, h->blk_row, h->col, h->row_ptr, h->pos_up, h->pos_lo, h->Li, h->S, h->Sn, 0);
-            return launch_err(h, "k_cg_factor/scale");
-        });
-        h->sn_valid = scale;
-        if (rc) return rc;
-        hmark(h, "factor/scale");
-        if (h->tlon && (rc = run_tl_setup(h, cams))) return rc;
-        hmark(h, "tl setup");
-        int* st = reinterpret_cast<int*>(h->host_res + 8);
-        rc = (h->tlon && h->prog_host) ? run_tl_cg(h, st) : run_bj_cg(h, st);
-        if (rc) return rc;
-        if (h->cgp_lost) {  // k_tl_cgp aborted (it left r0 alone): the CG again from the basis, launch path
-            h->cgp_lost = false;
-            HIPCHK(hipMemsetAsync(h->cg.status, 0, sizeof(int) * 4, h->stream));
-            if ((rc = ensure_sn(h)) || (rc = run_tl_basis(h, cams, h->stream)) || (rc = reissue_chain(h)) ||
-                (rc = run_tl_cg(h, st)))
-                return rc;
-        }
-        const int ci = cg_tail(h, st);
-        if (ci < 0) return ci;
-        iters = ci;
-        dcp = h->dc;
-    }
-    if (int rb = solve_tail(h, f, cams, pts_local, dcp)) return rb;
-    return iters;
-}
-
-// The back-substitution and the trial parameters of a solve (dcp: the camera step, null for a points-only solve).
-int solve_tail(insfm_ba* h, double f, const double* cams, const double* pts_local, const double* dcp) {
-    const bool gpk = h->kind == 1;
-    rec(h, 3);
-    if (gpk) {
-        if (h->Pl > 0)
-            k_gp_backsub<kGPG><<<h->n_gp_grp, kThreads, 0, h->stream>>>(h->Pl, h->pt_ptr, h->cam, h->gobs, dcp, h->Vinv, h->gp,
-                                                              pts_local, h->scl_cur, f, h->d.clamp_min, h->d.clamp_max, h->dp,
-                                                              h->pts_new, h->scl_new, h->ds, h->part_gp);
-        k_gp_update_cams<<<cdiv(3 * h->C, kThreads), kThreads, 0, h->stream>>>(3 * h->C, cams, dcp, h->cams_new);
-        int rc = launch_err(h, "k_gp_backsub/update");
-        if (rc) return rc;
-        return 0;
-    }
-    if (int rc0 = lin_join(h)) return rc0;  // the camera update reads U / g_c (points-only solves skip the factor)
-    const int rc = with_model(h->model, [&](auto mc) -> int {
-        constexpr int M = decltype(mc)::value;
-        const int nrun = h->Pl > 0 ? h->n_lin : 0;  // point runs, then the camera-update blocks
-        k_backsub_rc<M><<<nrun + h->n_gc, kLinThreads, 0, h->stream>>>(
-            h->lin_blk, h->pt_ptr, h->cam, h->ptl, h->uv, h->pp, cams, h->d.huber_delta, dcp, h->V, h->Vinv, h->gp,
-            pts_local, h->dp, h->pts_new, h->part_gp, nrun, h->C, h->U, h->gc, h->d.rank == 0, h->cams_new, h->part_gc,
-            stamp_ptr(h, kStBacksub));
-        return launch_err(h, "k_backsub_rc");
-    });
-    if (rc) return rc;
-    hmark(h, "backsub");
-    return 0;
-}
-
-// A step that ended in an error with a k_tl_cgp status unread: wait for the launch and restart the barrier counters
-// (the next launch's epochs would otherwise not match what this one counted).
-void cgp_drop_pending(insfm_ba* h) {
-    if (!h->cgp_pending) return;
-    h->cgp_pending = false;
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipMemsetAsync(h->cgp_sync, 0, sizeof(unsigned) * kCgpSyncWords, h->stream);
-    h->cgp_epochs = 0;
-}
-
-// Multi-rank: every rank leaves k_tl_cgp after an abort on any rank (own status `st0`).  A rank whose k_tl_cgp
-// converged left its final CG vectors in place of r0, so r0 = L^-1 b is formed again from the completed S / b
-// (k_cg_factor without U / g_c: the same L, L^-1 and r0) before the basis / restriction and the launch-path CG.
-int cgp_collective_fallback(insfm_ba* h, int st0) {
-    std::fprintf(stderr, "[insfm] rank %d: a k_tl_cgp grid barrier timed out on %s rank; every rank continues on the "
-                         "launch-per-iteration CG\n", h->d.rank, st0 == 4 ? "this" : "another");
-    h->cgp_nb = 0;
-    h->cgp_lost = false;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemsetAsync(h->cgp_sync, 0, sizeof(unsigned) * kCgpSyncWords, h->stream));
-    h->cgp_epochs = 0;
-    HIPCHK(hipMemsetAsync(h->cg.status, 0, sizeof(int) * 4, h->stream));
-    const int rc = with_D(h->D, [&](auto dc_) -> int {
-        constexpr int DV = decltype(dc_)::value;
-        k_cg_factor<DV><<<cdiv(h->C, kWaves), kThreads, 0, h->stream>>>(h->C, h->row_ptr, h->S, h->b, h->Lf, h->Li, h->cg,
-                                                                       nullptr, nullptr, 1.0, 0.0, 0.0);
-        return launch_err(h, "k_cg_factor");
-    });
-    if (rc) return rc;
-    if (int r2 = ensure_sn(h)) return r2;
-    if (int r3 = run_tl_basis(h, h->cams_cur, h->stream)) return r3;
-    return reissue_chain(h);
-}
-
-// The persistent CG's factorization and coarse basis again on the completed S / b (no U / g_c added: the same L,
-// L^-1 and r0 = L^-1 b): k_cg_factor_basis, or (FACTOR_BASIS=0 builds) k_cg_factor and k_tl_basis.
-int refactor_for_cgp(insfm_ba* h, const double* cams) {
-    const int rc = with_D(h->D, [&](auto dc_) -> int {
-        constexpr int DV = decltype(dc_)::value;
-        if constexpr (DV != 3) {
-            if (h->basis_by_factor) {
-                k_cg_factor_basis<DV><<<cdiv(h->C, kWaves), kThreads, 0, h->stream>>>(
-                    h->C, h->row_ptr, h->S, h->b, h->Lf, h->Li, h->cg, nullptr, nullptr, 1.0, 0.0, 0.0, cams, h->tl,
-                    h->cgp_runs + (size_t)h->cgp_grid * kCgpRows * 12);
-                return launch_err(h, "k_cg_factor_basis");
-            }
-        }
-        k_cg_factor<DV><<<cdiv(h->C, kWaves), kThreads, 0, h->stream>>>(h->C, h->row_ptr, h->S, h->b, h->Lf, h->Li, h->cg,
-                                                                       nullptr, nullptr, 1.0, 0.0, 0.0);
-        return launch_err(h, "k_cg_factor");
-    });
-    if (rc) return rc;
-    return h->basis_by_factor ? 0 : run_tl_basis(h, cams, h->stream);
-}
-
-// An A-DEF2 solve that broke down (k_tl_cgp status 2).  Its soundness rests on the coarse start x0 making
-// Z~^T r exactly zero, which holds only with the solve's own coarse inverse; under the lag rule E^-1 is the previous
-// solve's, the preconditioner is not symmetric on the iterates, and the single-reduction recurrence can break down.
-// The trial's solve is then repeated with the additive coarse correction (precond 1, symmetric for any SPD E^-1) on
-// the same handle: r0 = L^-1 b, the basis and the restriction of r0 again from the completed S / b
-// (refactor_for_cgp), one additive k_tl_cgp launch.  Every rank of a replicated
-// multi-rank CG sees the same status (bitwise-equal fixed-order arithmetic), so every rank repeats it.
-int adef2_fallback(insfm_ba* h, int it_failed, int* st) {
-    std::fprintf(stderr, "[insfm] A-DEF2 PCG breakdown at iteration %d: the trial's solve is repeated with the additive "
-                         "coarse correction\n", it_failed);
-    ++h->adef2_fallbacks;
-    HIPCHK(hipMemsetAsync(h->cg.status, 0, sizeof(int) * 4, h->stream));
-    int rc = refactor_for_cgp(h, h->cams_cur);
-    if (rc) return rc;
-    h->adef2 = false;
-    rc = run_tl_cg(h, st);
-    h->adef2 = true;
-    return rc;
-}
-
-// lm_step's accept rule for the trial being costed (k_publish copies an accepted trial into the caller's buffers)
-struct TrialAccept {
-    double last;     // the loss before the step
-    int can_reject;  // rejects < max_rejects
-};
-
-// The cost result to the host: k_publish into host-mapped memory and a spin on its sequence word; without the mapped
-// block, a copy and a stream synchronization.
-// Sets h->trial_copied when k_publish also copied an accepted trial (h->pub_host[5] holds its decision).
-int finish_cost(insfm_ba* h, const TrialAccept* ta) {
-    h->trial_copied = false;
-    if (!h->pub_host) {
-        HIPCHK(hipMemcpyAsync(h->host_res, h->result, sizeof(double) * 6, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return 0;
-    }
-    if (++h->pub_seq == 0) h->pub_seq = 1;
-    const unsigned seq = h->pub_seq;
-    const bool copy = ta != nullptr && h->ext_cur && h->kind == 0;
-    const long long ncam = copy ? (long long)h->C * h->stride : 0, npts = copy ? (long long)h->Pl * 3 : 0;
-    const int grid = copy ? std::max(1, std::min(1024, cdiv(std::max(ncam, npts / 2 + 1), kThreads))) : 1;
-    k_publish<<<grid, kThreads, 0, h->stream>>>(h->result, h->cgp_pending ? h->cg.status : nullptr, h->pub_dev, seq,
-                                               ta ? ta->last : 0.0, ta ? ta->can_reject : 0,
-                                               h->cams_new, copy ? h->cams_cur : nullptr, ncam, h->pts_new, h->pts_cur, npts,
-                                               stamp_ptr(h, kStPublish));
-    if (int rc = launch_err(h, "k_publish")) return rc;
-    hmark(h, "publish");
-    const unsigned* w = reinterpret_cast<const unsigned*>(h->pub_host + 8);
-    // bounded like the CG poll: a device that neither publishes nor reports an error ends the step with EHIP
-    static const double stall_s = 6.0 * cg_stall_limit_s(std::getenv("INSFM_CG_STALL_S"));
-    const double t_wait = wall_seconds();
-    for (unsigned n = 1;; ++n) {
-        if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == seq) break;
-        if ((n & 255) == 0) {
-            const hipError_t q = hipStreamQuery(h->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) {
-                h->err = std::string("cost: ") + hipGetErrorString(q);
-                return INSFM_BA_EHIP;
-            }
-            if (q == hipSuccess && __atomic_load_n(w, __ATOMIC_ACQUIRE) != seq) {
-                h->err = "cost: the stream drained without publishing the result";
-                return INSFM_BA_EHIP;
-            }
-            if (wall_seconds() - t_wait > stall_s) {
-                h->err = "cost: no result from the device for " + std::to_string(stall_s) +
-                         " s (INSFM_CG_STALL_S scales the limit)";
-                return INSFM_BA_EHIP;
-            }
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    hmark(h, "published");
-    const volatile double* pv = h->pub_host;
-    for (int k = 0; k < 5; ++k) h->host_res[k] = pv[k];
-    h->host_res[5] = pv[6];  // k_tl_cgp aborts (summed over the ranks)
-    h->trial_copied = copy;
-    return 0;
-}
-
-// cost at (cams, pts_local) -> h->result[0..1]; with gain partials when `gains` (after a solve).
-int run_cost(insfm_ba* h, const double* cams, const double* pts_local, bool gains, const double* scl = nullptr,
-             const TrialAccept* ta = nullptr) {
-    if (h->kind == 1) {
-        if (h->Nl > 0)
-            k_gp_cost<<<h->n_cost, kThreads, 0, h->stream>>>(h->Nl, h->cam, h->ptl, h->trans, h->fcam, cams, pts_local, scl,
-                                                             h->d.huber_delta, h->part_cost);
-        k_final<<<1, kFinalThreads, 0, h->stream>>>(h->part_cost, h->Nl > 0 ? h->n_cost : 0, gains && h->Pl > 0 ? h->part_gp : nullptr,
-                                               h->n_gp, nullptr, 0, h->flags, h->result, nullptr);
-        int rc = launch_err(h, "k_gp_cost/k_final");
-        if (rc) return rc;
-        h->flags_dirty = false;
-        rc = allreduce(h, h->result, 6);
-        if (rc) return rc;
-        return finish_cost(h, nullptr);
-    }
-    int rc = with_model(h->model, [&](auto mc) -> int {
-        constexpr int M = decltype(mc)::value;
-        if (h->Nl > 0)
-            k_cost<M><<<h->n_cost, kCostThreads, 0, h->stream>>>(h->Nl, h->cam, h->ptl, h->uv, h->pp, cams, pts_local,
-                                                             h->d.huber_delta, h->part_cost,
-                                                             gains ? stamp_ptr(h, kStCost) : nullptr);
-        k_final<<<1, kFinalThreads, 0, h->stream>>>(h->part_cost, h->Nl > 0 ? h->n_cost : 0, gains && h->Pl > 0 ? h->part_gp : nullptr,
-                                               h->n_gp, gains ? h->part_gc : nullptr, h->n_gc, h->flags, h->result,
-                                               h->cgp_pending ? h->cg.status : nullptr,
-                                               gains ? stamp_ptr(h, kStFinal) : nullptr);
-        return launch_err(h, "k_cost/k_final");
-    });
-    if (rc) return rc;
-    h->flags_dirty = false;
-    rc = allreduce(h, h->result, 6);
-    if (rc) return rc;
-    return finish_cost(h, ta);
-}
-
-// One LM step on the parameters loaded into cams_cur / pts_cur (/ scl_cur): bae.optim.LM.step semantics (SURVEY.md
-// 3.3): cumulative damping, TrustRegion radius update, up to max_rejects rejected trials.
-int lm_step(insfm_ba* h, insfm_ba_stats* st) {
-    h->timing = st != nullptr && h->want_timing;
-    for (auto& v : h->tms) v = 0.0;
-    h->cg_launches = 0;
-    int rc;
-    if (!h->have_loss) {
-        if ((rc = run_cost(h, h->cams_cur, h->pts_cur, false, h->scl_cur))) return rc;
-        h->loss = h->host_res[0];
-        h->have_loss = true;
-    }
-    const double last = h->loss;
-    h->hmarks.clear();
-    hmark(h, "step");
-    if (h->stamps)  // (this step's slot of the ring: a kernel not launched in the step reads 0, not a stamp of 1024 ago)
-        HIPCHK(hipMemsetAsync(stamp_ptr(h, 0), 0, sizeof(long long) * kStKinds * 2, h->stream));
-    rec(h, 0);
-    if ((rc = run_linearize(h, h->cams_cur, h->pts_cur))) return rc;
-    hmark(h, "linearize enqueued");
-    if (h->timing && (rc = lin_join(h))) return rc;  // (the phase split times both linearization kernels)
-    rec(h, 1);
-    double f = 1.0;
-    int rejects = 0, trials = 0, pcg_total = 0, pcg_last = 0, failed = 0;
-    cgp_drop_pending(h);
-    for (;;) {
-        f *= (1.0 + h->damping);
-        ++trials;
-        h->cg_async = true;  // (a k_tl_cgp solve: its status is read after the trial's cost, below)
-        int it = run_solve(h, f, h->cams_cur, h->pts_cur);
-        h->cg_async = false;
-        if (it == INSFM_BA_ESOLVER) { failed = 1; h->loss = last; break; }
-        if (it < 0) return it;
-        rec(h, 4);
-        const TrialAccept ta{last, rejects < h->d.max_rejects ? 1 : 0};
-        if ((rc = run_cost(h, h->cams_new, h->pts_new, true, h->scl_new, &ta))) return rc;  // waits for the result
-        if (h->cgp_pending) {  // the k_tl_cgp launch finished before the k_publish the host just saw
-            h->cgp_pending = false;
-            int cst[3];
-            if ((rc = cgp_complete(h, cst))) return rc;
-            if (h->timing) acc_time(h, 8, 9, 5);
-            if (h->host_res[4] != 0.0) { failed = 1; h->loss = last; break; }  // a damped point block was not SPD
-            const bool multi = h->d.world_size > 1 || h->d.allreduce;
-            if (multi && h->host_res[5] != 0.0) {
-                // a replicated multi-rank CG: some rank's k_tl_cgp timed out at a grid barrier (the all-reduced flag,
-                // the same on every rank, and k_publish accepted nowhere).  Every rank leaves the persistent CG for
-                // good and repeats this trial's solve on the launch path from r0 -- the same fixed-order arithmetic
-                // everywhere, so the ranks' dc stay bitwise equal -- then its back-substitution and cost.
-                if ((rc = cgp_collective_fallback(h, cst[0]))) return rc;
-                int* st = reinterpret_cast<int*>(h->host_res + 8);
-                if ((rc = run_tl_cg(h, st))) return rc;
-                it = cg_tail(h, st);
-                if (it == INSFM_BA_ESOLVER) { failed = 1; h->loss = last; break; }
-                if (it < 0) return it;
-                if ((rc = solve_tail(h, f, h->cams_cur, h->pts_cur, h->dc))) return rc;
-                if ((rc = run_cost(h, h->cams_new, h->pts_new, true, h->scl_new, &ta))) return rc;
-            } else if (cst[0] == 4 && h->cgp_lost) {
-                // single rank: a grid barrier timed out (cgp_complete switched the handle to the launch path); this
-                // trial's CG again from the basis, then its back-substitution and cost (k_publish rejected the first)
-                h->cgp_lost = false;
-                HIPCHK(hipMemsetAsync(h->cg.status, 0, sizeof(int) * 4, h->stream));
-                int* st = reinterpret_cast<int*>(h->host_res + 8);
-                if ((rc = ensure_sn(h)) || (rc = run_tl_basis(h, h->cams_cur, h->stream)) || (rc = reissue_chain(h)) ||
-                    (rc = run_tl_cg(h, st)))
-                    return rc;
-                it = cg_tail(h, st);
-                if (it == INSFM_BA_ESOLVER) { failed = 1; h->loss = last; break; }
-                if (it < 0) return it;
-                if ((rc = solve_tail(h, f, h->cams_cur, h->pts_cur, h->dc))) return rc;
-                if ((rc = run_cost(h, h->cams_new, h->pts_new, true, h->scl_new, &ta))) return rc;
-            } else if (cst[0] == 2 && h->adef2) {
-                // A-DEF2 breakdown: this trial's solve again with the additive coarse correction (adef2_fallback),
-                // then its back-substitution and cost (k_publish rejected the first: its CG did not converge)
-                int* st = reinterpret_cast<int*>(h->host_res + 8);
-                if ((rc = adef2_fallback(h, cst[1], st))) return rc;
-                it = cg_tail(h, st);
-                if (it == INSFM_BA_ESOLVER) { failed = 1; h->loss = last; break; }
-                if (it < 0) return it;
-                if ((rc = solve_tail(h, f, h->cams_cur, h->pts_cur, h->dc))) return rc;
-                if ((rc = run_cost(h, h->cams_new, h->pts_new, true, h->scl_new, &ta))) return rc;
-            } else if (cst[0] != 1) {
-                h->err = std::string("PCG ") + (cst[0] == 2 ? "breakdown" : "timed out (a k_tl_cgp grid barrier)") +
-                         " at iteration " + std::to_string(cst[1]) + " (status " + std::to_string(cst[0]) + ")";
-                if (cst[0] == 2) { failed = 1; h->loss = last; break; }
-                return INSFM_BA_EHIP;
-            } else {
-                it = cst[1];
-                h->coarse_used = cst[2];
-                h->last_cg_iters = it;
-            }
-        }
-        rec(h, 5);
-        if (h->timing) {
-            (void)hipEventSynchronize(h->ev[5]);
-            if (trials == 1) acc_time(h, 0, 1, 0);
-            if (h->d.optimize_poses) {
-                acc_time(h, 6, 7, 1);
-                acc_time(h, 1, 3, 2);
-                if (h->xstream) acc_time(h, 16, 17, 7);
-            }
-            acc_time(h, 3, 4, 3);
-            acc_time(h, 4, 5, 4);
-            rec(h, 1);  // the next trial starts here
-        }
-        if (h->trial_copied && (h->host_res[4] != 0.0 || (last < h->host_res[0] && rejects < h->d.max_rejects)) &&
-            h->pub_host[5] != 0.0) {  // (cannot happen: the same rule on the same doubles)
-            h->err = "k_publish accepted a trial the host rejects";
-            return INSFM_BA_EHIP;
-        }
-        if (h->host_res[4] != 0.0) { failed = 1; h->loss = last; break; }  // a damped point block was not SPD
-        pcg_last = it;
-        pcg_total += it;
-        const double loss_new = h->host_res[0];
-        const double denom = h->host_res[2] + h->host_res[3];
-        const double quality = (last - loss_new) / denom;
-        double radius = 1.0 / h->damping;
-        if (quality > h->d.tr_high) { radius = h->d.tr_up * radius; h->down = h->d.tr_down; }
-        else if (quality > h->d.tr_low) { h->down = h->d.tr_down; }
-        else { radius = radius * h->down; h->down = h->down * h->d.tr_factor; }
-        radius = std::min(std::max(radius, h->d.tr_min), h->d.tr_max);
-        h->damping = 1.0 / radius;
-        if (last < loss_new && rejects < h->d.max_rejects) {
-            ++rejects;
-            h->loss = last;
-            continue;
-        }
-        if (h->trial_copied) {  // k_publish already copied the accepted trial into the caller's buffers
-            if (h->pub_host[5] != 1.0) {
-                h->err = "accept decision of k_publish differs from the host's";
-                return INSFM_BA_EHIP;
-            }
-        } else if (h->ext_cur) {  // the current parameters live in the caller's buffers: copy the accepted trial there
-            HIPCHK(hipMemcpyAsync(h->cams_cur, h->cams_new, sizeof(double) * (size_t)h->C * h->stride,
-                                  hipMemcpyDeviceToDevice, h->stream));
-            if (h->Pl)
-                HIPCHK(hipMemcpyAsync(h->pts_cur, h->pts_new, sizeof(double) * (size_t)h->Pl * 3, hipMemcpyDeviceToDevice,
-                                      h->stream));
-        } else {
-            std::swap(h->cams_cur, h->cams_new);
-            std::swap(h->pts_cur, h->pts_new);
-        }
-        std::swap(h->scl_cur, h->scl_new);
-        h->loss = loss_new;
-        break;
-    }
-    if (h->timing) harvest_chain_time(h);
-    if (st) {
-        st->loss = h->loss;
-        st->loss_before = last;
-        st->damping = h->damping;
-        st->trials = trials;
-        st->rejects = rejects;
-        st->pcg_iters_last = pcg_last;
-        st->pcg_iters_total = pcg_total;
-        st->solver_failed = failed;
-        for (int k = 0; k < 8; ++k) st->time_ms[k] = h->tms[k];
-        st->cg_launches = h->cg_launches;
-        st->coarse_used = h->coarse_used;
-    }
-    h->timing = false;
-    if (h->stamps) ++h->stamp_step;
-    if (host_trace2() && !h->hmarks.empty()) {
-        hmark(h, "step end");
-        std::string line = "[insfm host2]";
-        for (auto& m : h->hmarks) line += " " + std::string(m.first) + "=" + std::to_string((int)(1e6 * (m.second - h->hmarks[0].second)));
-        std::fprintf(stderr, "%s\n", line.c_str());
-    }
-    return 0;
-}
-
-}  // namespace
+#include "ba_solve.h"
+#include "ba_step.h"
 
 // ============================================================================================================
 // C ABI
@@ -2928,126 +1743,11 @@ int32_t insfm_ba_cg_fallbacks(const insfm_ba* h) {
     return h->adef2_fallbacks;
 }
 
-int32_t insfm_ba_debug_stamps(insfm_ba* h, int64_t* host_out, int32_t max_steps) {
-    if (!h || !host_out || max_steps < 0) return INSFM_BA_EINVAL;
-    if (!h->stamps) return 0;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const long long n = std::min<long long>(std::min<long long>(h->stamp_step, kStampSteps), max_steps);
-    std::vector<long long> ring((size_t)kStampSteps * kStKinds * 2);
-    HIPCHK(hipMemcpy(ring.data(), h->stamps, sizeof(long long) * ring.size(), hipMemcpyDeviceToHost));
-    const long long first = h->stamp_step - n;  // the oldest of the last n steps
-    for (long long q = 0; q < n; ++q) {
-        const size_t src = (size_t)((first + q) % kStampSteps) * kStKinds * 2;
-        std::memcpy(host_out + (size_t)q * kStKinds * 2, ring.data() + src, sizeof(long long) * kStKinds * 2);
-    }
-    return (int32_t)n;
-}
-
 int insfm_ba_set_persistent_cg(insfm_ba* h, int32_t on) {
     if (!h) return INSFM_BA_EINVAL;
     if (on) return h->cgp_nb ? INSFM_BA_OK : INSFM_BA_EINVAL;  // (cannot turn on what create found ineligible)
     cgp_drop_pending(h);
     h->cgp_nb = 0;
-    return INSFM_BA_OK;
-}
-
-int insfm_ba_cg_window(insfm_ba* h, void* ipc_handle) {
-    if (!h || !ipc_handle) return INSFM_BA_EINVAL;
-    if (h->kind != 0 || h->d.world_size < 2 || !h->tlon || h->tl.Racc || h->xwin) {
-        h->err = "cg_window: needs a multi-rank two-level handle (precond 1) that has no window yet";
-        return INSFM_BA_EINVAL;
-    }
-    h->cgp_nb = 0;  // (the partitioned launch path replaces the replicated persistent CG)
-    const int C = h->C, D = h->D, MC = D + 1, W = h->d.world_size;
-    const long long region = (long long)C * D + 3LL * C + (long long)C * MC + 2;
-    h->xoff_region[0] = 0;
-    h->xoff_region[1] = region;
-    h->xoff_xg = 2 * region;
-    h->xoff_flags = h->xoff_xg + (long long)C * D;
-    h->xwin_bytes = sizeof(double) * (size_t)h->xoff_flags + sizeof(unsigned) * kXFlagStride * 2 * (size_t)W;
-    // uncached device memory: peers write into it over their mappings, and no cache of this device keeps a stale line
-    hipError_t e = hipExtMallocWithFlags(reinterpret_cast<void**>(&h->xwin), h->xwin_bytes, hipDeviceMallocUncached);
-    if (e == hipSuccess) e = hipMemsetAsync(h->xwin, 0, h->xwin_bytes, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipIpcGetMemHandle(reinterpret_cast<hipIpcMemHandle_t*>(ipc_handle), h->xwin);
-    if (e != hipSuccess) {
-        h->err = std::string("cg_window: ") + hipGetErrorString(e);
-        return INSFM_BA_EHIP;
-    }
-    return INSFM_BA_OK;
-}
-
-int insfm_ba_cg_attach(insfm_ba* h, const void* handles) {
-    if (!h || !handles || !h->xwin || h->xpart) return INSFM_BA_EINVAL;
-    const int W = h->d.world_size, C = h->C;
-    std::vector<double*> bases(W, nullptr);
-    std::vector<unsigned*> flags(W, nullptr);
-    for (int r = 0; r < W; ++r) {
-        if (r == h->d.rank) {
-            bases[r] = h->xwin;
-        } else {
-            void* q = nullptr;
-            hipIpcMemHandle_t hd;
-            std::memcpy(&hd, static_cast<const char*>(handles) + (size_t)r * sizeof(hipIpcMemHandle_t), sizeof(hd));
-            const hipError_t e = hipIpcOpenMemHandle(&q, hd, hipIpcMemLazyEnablePeerAccess);
-            if (e != hipSuccess) {
-                h->err = std::string("cg_attach: rank ") + std::to_string(r) + ": " + hipGetErrorString(e);
-                return INSFM_BA_EHIP;
-            }
-            h->xopened.push_back(q);
-            bases[r] = static_cast<double*>(q);
-        }
-        flags[r] = reinterpret_cast<unsigned*>(bases[r] + h->xoff_flags);
-    }
-    int rc = 0;
-    if ((rc = dalloc(h, reinterpret_cast<void**>(&h->xbases), sizeof(double*) * W))) return rc;
-    if ((rc = dalloc(h, reinterpret_cast<void**>(&h->xpflags), sizeof(unsigned*) * W))) return rc;
-    if ((rc = dalloc(h, reinterpret_cast<void**>(&h->xcnt), sizeof(unsigned) * 2))) return rc;
-    HIPCHK(hipMemcpyAsync(h->xbases, bases.data(), sizeof(double*) * W, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->xpflags, flags.data(), sizeof(unsigned*) * W, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->xcnt, 0, sizeof(unsigned) * 2, h->stream));
-    // rows: the cluster-ordered positions split at cluster boundaries, rank r from the boundary nearest r C / W
-    const std::vector<int>& lab = h->clab_host;
-    std::vector<int> bnd;  // cluster-ordered boundaries (positions where a cluster starts), incl. 0 and C
-    {
-        std::vector<int> size(h->tl.nc, 0);
-        for (int i = 0; i < C; ++i) size[lab[i]]++;
-        int q = 0;
-        for (int c = 0; c < h->tl.nc; ++c) { bnd.push_back(q); q += size[c]; }
-        bnd.push_back(q);
-    }
-    h->xq.assign(W + 1, C);
-    h->xq[0] = 0;
-    for (int r = 1; r < W; ++r) {
-        const long long target = (long long)r * C / W;
-        int best = bnd[0];
-        for (int b : bnd)
-            if (std::llabs(b - target) < std::llabs(best - target)) best = b;
-        h->xq[r] = std::max(best, h->xq[r - 1]);
-    }
-    // the basis writes r0 and its restriction into region 1 (what the setup k_tl_pc reads)
-    h->tl = tl_region(h, 1);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->xpart = true;
-    return INSFM_BA_OK;
-}
-
-int insfm_ba_debug_time_xchg(insfm_ba* h, int32_t reps, double* us) {
-    if (!h || !us || !h->xpart || reps < 1) return INSFM_BA_EINVAL;
-    HIPCHK(hipEventRecord(h->ev[10], h->stream));
-    for (int r = 0; r < reps; ++r) launch_xchg(h, 1);  // (slot 1: not gated by the CG status)
-    HIPCHK(hipEventRecord(h->ev[11], h->stream));
-    HIPCHK(hipEventSynchronize(h->ev[11]));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[10], h->ev[11]));
-    *us = 1e3 * ms / reps;
-    return INSFM_BA_OK;
-}
-
-int insfm_ba_cg_partition(const insfm_ba* h, int32_t* rows_begin_end) {
-    if (!h || !rows_begin_end || !h->xpart) return INSFM_BA_EINVAL;
-    rows_begin_end[0] = h->xq[h->d.rank];
-    rows_begin_end[1] = h->xq[h->d.rank + 1];
     return INSFM_BA_OK;
 }
 
@@ -3093,254 +1793,6 @@ int insfm_ba_step(insfm_ba* h, double* cams_user, double* pts_user, insfm_ba_sta
     h->pts_cur = ip;
     h->ext_cur = false;
     return rc;
-}
-
-int insfm_ba_debug_linearize(insfm_ba* h, const double* cams, const double* pts) {
-    if (!h || !cams || !pts || h->kind != 0) return INSFM_BA_EINVAL;
-    cgp_drop_pending(h);
-    h->keep_S = 1;
-    HIPCHK(hipMemcpyAsync(h->cams_cur, cams, sizeof(double) * (size_t)h->C * h->stride, hipMemcpyDeviceToDevice, h->stream));
-    if (h->Pl)
-        HIPCHK(hipMemcpyAsync(h->pts_cur, pts + 3 * (size_t)h->p0, sizeof(double) * (size_t)h->Pl * 3, hipMemcpyDeviceToDevice,
-                              h->stream));
-    int rc = run_linearize(h, h->cams_cur, h->pts_cur);
-    if (!rc) rc = lin_join(h);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-int insfm_ba_debug_solve(insfm_ba* h, double f) {
-    if (!h) return INSFM_BA_EINVAL;
-    cgp_drop_pending(h);
-    h->keep_S = 1;
-    // solves around the parameters last passed to insfm_ba_debug_linearize
-    int it = run_solve(h, f, h->cams_cur, h->pts_cur);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return it;
-}
-
-int insfm_ba_debug_spd_inverse(int32_t m, const double* E, double* Einv, void* stream, int32_t reps,
-                               double* us_per_inverse) {
-    if (m < 1 || m > 4096 || !E || !Einv) return INSFM_BA_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nB = gj_steps(m), ld = nB * kGB;
-    const int n = reps > 0 && us_per_inverse ? reps : 1;
-    // the padded, identity-extended copy and the equilibration d = 1 / sqrt(diag E) are built on the host
-    std::vector<double> Eh((size_t)m * m), Ep((size_t)ld * ld, 0.0), dh(ld, 1.0);
-    if (hipMemcpy(Eh.data(), E, sizeof(double) * Eh.size(), hipMemcpyDeviceToHost) != hipSuccess) return INSFM_BA_EHIP;
-    for (int r = 0; r < ld; ++r)
-        for (int c = 0; c < ld; ++c)
-            Ep[(size_t)r * ld + c] = (r < m && c < m) ? Eh[(size_t)r * m + c] : (r == c ? 1.0 : 0.0);
-    for (int r = 0; r < m; ++r) dh[r] = 1.0 / std::sqrt(Eh[(size_t)r * m + r]);
-    double *Ew = nullptr, *Ww = nullptr, *dd = nullptr, *Pw = nullptr;
-    int* ok = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int okh = 0;
-    float ms = 0.f;
-    hipError_t e = hipMalloc(&Ew, sizeof(double) * (size_t)ld * ld);
-    if (e == hipSuccess) e = hipMalloc(&Ww, sizeof(double) * (size_t)ld * ld);
-    if (e == hipSuccess) e = hipMalloc(&dd, sizeof(double) * ld);
-    if (e == hipSuccess) e = hipMalloc(&Pw, sizeof(double) * 2 * kGB * kGB);
-    if (e == hipSuccess) e = hipMalloc(&ok, sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dd, dh.data(), sizeof(double) * ld, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    for (int r = 0; r < n && e == hipSuccess; ++r) {
-        e = hipMemcpyAsync(Ew, Ep.data(), sizeof(double) * Ep.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipEventRecord(e0, st);
-        for (int u = 0; u <= nB && e == hipSuccess; ++u) {
-            launch_gj_unit(u, m, Ew, Ww, Pw, dd, Einv, ok, st);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float t = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-        ms += t;
-    }
-    if (e == hipSuccess) e = hipMemcpy(&okh, ok, sizeof(int), hipMemcpyDeviceToHost);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(Ew); (void)hipFree(Ww); (void)hipFree(dd); (void)hipFree(Pw); (void)hipFree(ok);
-    if (e != hipSuccess) return INSFM_BA_EHIP;
-    if (us_per_inverse) *us_per_inverse = 1e3 * ms / n;
-    return okh ? 1 : 0;
-}
-
-int insfm_ba_debug_time_kernel(insfm_ba* h, int32_t which, int32_t reps, double* us_per_launch) {
-    if (!h || reps <= 0 || !us_per_launch || !h->d.optimize_poses) return INSFM_BA_EINVAL;
-    // re-run one kernel `reps` times back to back on the data of the last solve; the CG state it overwrites is
-    // scratch once the solve has finished (dc already extracted).  0: k_cg_iter  1: k_schur (damping factor 1)
-    // 2: one two-level CG iteration  3: k_tl_pspmv  4: the two-level setup  5: k_lin_points (overwrites W / V / g_p)
-    HIPCHK(hipMemsetAsync(h->cg.status, 0, sizeof(int) * 4, h->stream));
-    HIPCHK(hipMemsetAsync(h->cg.scal, 0, sizeof(double) * 4, h->stream));
-    if (((which >= 2 && which <= 4) || which == 6 || which == 7) && !h->tlon) return INSFM_BA_EINVAL;
-    if (which == 5 && (h->kind != 0 || !h->W)) return INSFM_BA_EINVAL;
-    if (which < 0 || which > 7) return INSFM_BA_EINVAL;
-    if (int rc0 = side_flush(h)) return rc0;  // its pending E build / factorization must not interleave
-    if (int rc0 = lin_join(h)) return rc0;
-    if (which != 1 && which != 5 && which != 6)
-        if (int rc0 = ensure_sn(h)) return rc0;  // (kernels that read the scaled copy Sn)
-    if (which == 2 && h->tl.Racc) {
-        // atomic cluster sums: iteration 1's k_tl_pc reads buffer 1 every repetition (its k_tl_pspmv adds into buffer
-        // 0, which the next repetition clears), so fill buffer 1 once from a k_tl_pspmv of iteration 0
-        HIPCHK(hipMemsetAsync(h->tl.Racc + h->tl.m, 0, sizeof(double) * h->tl.m, h->stream));
-        HIPCHK(hipMemsetAsync(h->tl.Gacc + 3 * h->tl.nc, 0, sizeof(double) * 3 * h->tl.nc, h->stream));
-        with_D(h->D, [&](auto dc_) -> int {
-            constexpr int DV = decltype(dc_)::value;
-            k_tl_pspmv<DV><<<h->C, kPspmvThreads, 0, h->stream>>>(0, h->C, h->nbr_stride, h->nbr_ptr, h->nbr_j, h->Sn,
-                                                                 h->Lf, h->cg, h->tl, XPart{});
-            return 0;
-        });
-    }
-    HIPCHK(hipEventRecord(h->ev[10], h->stream));
-    int rc = with_D(h->D, [&](auto dc_) -> int {
-        constexpr int DV = decltype(dc_)::value;
-        for (int r = 0; r < reps; ++r) {
-            if (which == 2) {
-                launch_tl_iter<DV>(h, 1, h->d.pcg_max_iter, 0.0);
-            } else if (which == 3) {
-                k_tl_pspmv<DV><<<h->C, kPspmvThreads, 0, h->stream>>>(1, h->C, h->nbr_stride, h->nbr_ptr, h->nbr_j, h->Sn, h->Lf, h->cg,
-                                                                   h->tl, XPart{});
-            } else if (which == 4) {
-                int rc2 = run_tl_basis(h, h->cams_cur, h->stream);
-                if (!rc2) rc2 = run_tl_build(h, 0, h->stream);
-                for (int u = 0; u <= gj_steps(h->tl.m) && !rc2; ++u) rc2 = run_tl_gj_unit(h, 0, u, h->stream);
-                if (rc2) return rc2;
-            } else if (which == 6) {  // the coarse inverse alone: k_gj_pinv0 + nB x k_gj_step on slot 0's E
-                for (int u = 1; u <= gj_steps(h->tl.m) + 1; ++u)
-                    if (int rc2 = run_tl_gj_unit(h, 0, u - 1, h->stream)) return rc2;
-            } else if (which == 7) {  // the E build alone: k_tl_erow + k_tl_ereduce
-                if (int rc2 = run_tl_build(h, 0, h->stream)) return rc2;
-            } else if (which == 5 && h->kind == 0 && h->W) {  // k_lin_points at the last trial's parameters
-                with_model(h->model, [&](auto mc) -> int {
-                    constexpr int M = decltype(mc)::value;
-                    if (h->Pl > 0) launch_lin_points_w<M>(h, h->cams_new, h->pts_new, first_trial_prep(h));
-                    return 0;
-                });
-            } else if (which == 0)
-                k_cg_iter<DV><<<h->C, kCgThreads, 0, h->stream>>>(1, h->C, h->d.pcg_max_iter, 0.0, h->nbr_ptr, h->nbr_j, h->Sn,
-                                                                h->Lf, h->cg);
-            else {  // the k_schur form this handle runs (deterministic mode: one wave per workgroup, its LDS layout)
-                const int rc2 = launch_schur(h, h->kind ? h->Up : h->U, h->kind ? h->gpc : h->gc, 1.0,
-                                             h->kind ? -1e308 : h->d.clamp_min, h->kind ? 1e308 : h->d.clamp_max,
-                                             h->kind ? 1 : h->d.rank == 0, false);
-                if (rc2) return rc2;
-            }
-        }
-        return launch_err(h, "debug_time_kernel");
-    });
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(h->ev[11], h->stream));
-    HIPCHK(hipEventSynchronize(h->ev[11]));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[10], h->ev[11]));
-    *us_per_launch = 1e3 * ms / reps;
-    return INSFM_BA_OK;
-}
-
-int insfm_ba_debug_time_cgp(insfm_ba* h, int32_t reps, double* out) {
-    // the persistent CG of the last solve again, `reps` times: k_cg_factor_basis on the completed S / b (no U / g_c
-    // added: the same L, L^-1 and r0 = L^-1 b; Z~ and the restriction of r0), then the timed part -- the k_tl_cgp
-    // launch, bracketed by events -- with the coarse segments written as in a lagged solve.  out[0] us per
-    // k_tl_cgp launch, out[1] 0 (the setup launch k_tl_pc that preceded it until round 4 is folded in), out[2]
-    // iterations (mean).
-    if (!h || reps <= 0 || !out || !h->cgp_nb || h->kind != 0 || !h->prog_host) return INSFM_BA_EINVAL;
-    cgp_drop_pending(h);
-    if (int rc0 = side_flush(h)) return rc0;
-    if (int rc0 = lin_join(h)) return rc0;
-    const int maxit = h->d.pcg_max_iter;
-    const double tol2 = h->d.pcg_tol * h->d.pcg_tol;
-    double t_cg = 0.0, t_pc = 0.0, iters = 0.0;
-    for (int r = 0; r < reps; ++r) {
-        HIPCHK(hipMemsetAsync(h->cg.status, 0, sizeof(int) * 4, h->stream));
-        if (int rc = refactor_for_cgp(h, h->cams_new)) return rc;  // (the last trial's cameras)
-        volatile int* pg = h->prog_host;
-        pg[0] = pg[1] = pg[2] = pg[3] = 0;
-        std::atomic_thread_fence(std::memory_order_seq_cst);
-        h->cgp_defer = true;  // (oseg: the segments are written, as in the lagged solves that are most of a run)
-        HIPCHK(hipEventRecord(h->ev[10], h->stream));
-        if (int rc2 = launch_tl_cgp(h, maxit, tol2)) { h->cgp_defer = false; return rc2; }
-        h->cgp_defer = false;
-        h->cgp_tag += (unsigned)maxit + 3u;
-        HIPCHK(hipEventRecord(h->ev[11], h->stream));
-        HIPCHK(hipEventSynchronize(h->ev[11]));
-        int st[3];
-        if (int rc2 = cgp_complete(h, st)) return rc2;
-        if (st[0] != 1) {
-            h->err = "debug_time_cgp: the CG ended with status " + std::to_string(st[0]);
-            return st[0] == 2 ? INSFM_BA_ESOLVER : INSFM_BA_EHIP;
-        }
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev[10], h->ev[11]));
-        t_cg += ms;
-        iters += st[1];
-    }
-    // (round 5: the coarse solve of r0 runs inside k_tl_cgp; no setup launch in front of it)
-    out[1] = t_pc;
-    out[0] = 1e3 * t_cg / reps;
-    out[2] = iters / reps;
-    return INSFM_BA_OK;
-}
-
-int32_t insfm_ba_debug_clusters(const insfm_ba* h, int32_t* labels) {
-    if (!h) return INSFM_BA_EINVAL;
-    if (!h->tlon) return 0;
-    if (labels) std::memcpy(labels, h->clab_host.data(), sizeof(int32_t) * h->C);
-    return h->tl.nc;
-}
-
-int64_t insfm_ba_debug_get(insfm_ba* h, int32_t which, double* host) {
-    if (!h || !host) return INSFM_BA_EINVAL;
-    const size_t C = h->C, Pl = h->Pl, Nl = h->Nl, D = h->D;
-    const double* src = nullptr;
-    size_t n = 0;
-    switch (which) {
-        case 0: src = h->W; n = Nl * D * 3; break;
-        case 1: src = h->V; n = Pl * 6; break;
-        case 2: src = h->gp; n = Pl * 3; break;
-        case 3: src = h->U; n = C * D * D; break;
-        case 4: src = h->gc; n = C * D; break;
-        case 5: {  // the scaled upper blocks S~ (diagonal: I), assembled from the row-contiguous copy Sn
-            if (h->kind != 0 && h->kind != 1) return INSFM_BA_EINVAL;
-            if (int rc0 = side_flush(h)) return rc0;
-            if (int rc0 = ensure_sn(h)) return rc0;
-            const size_t DP = D + (D & 1), nb = (size_t)h->nnzb;
-            std::vector<double> sn((size_t)std::max<int64_t>(h->n_nbr, 1) * D * DP);
-            if (h->n_nbr) HIPCHK(hipMemcpyAsync(sn.data(), h->Sn, sizeof(double) * h->n_nbr * D * DP, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            std::vector<int> rp(C + 1);
-            HIPCHK(hipMemcpy(rp.data(), h->row_ptr, sizeof(int) * (C + 1), hipMemcpyDeviceToHost));
-            std::vector<char> diag_blk(nb, 0);
-            for (size_t i = 0; i < C; ++i) diag_blk[rp[i]] = 1;
-            for (size_t e = 0; e < nb; ++e)
-                for (size_t a = 0; a < D; ++a)
-                    for (size_t c = 0; c < D; ++c)
-                        host[(e * D + a) * D + c] = diag_blk[e] ? (a == c ? 1.0 : 0.0)
-                                                                : sn[((size_t)h->pos_up_host[e] * D + a) * DP + c];
-            return (int64_t)(nb * D * D);
-        }
-        case 6: src = h->b; n = C * D; break;
-        case 7: src = h->dc; n = C * D; break;
-        case 8: src = h->dp; n = Pl * 3; break;
-        // two-level internals (debug): 9 u, 10 w, 11 rowR, 12/13 E^-1 slot 0/1, 14 row partials [r.u | w.u], 15 r
-        case 9: src = h->tl.u; n = h->tlon ? C * D : 0; break;
-        case 10: src = h->cg.w[0]; n = C * D; break;
-        case 11: src = h->tl.rowR; n = h->tlon ? C * (D + 1) : 0; break;  // restriction row partials
-        case 12: src = h->Einvbuf[0]; n = h->tlon ? (size_t)h->tl.m * h->tl.m : 0; break;
-        case 13: src = h->Einvbuf[1]; n = h->tlon ? (size_t)h->tl.m * h->tl.m : 0; break;
-        case 14: src = h->tl.gd; n = h->tlon ? 2 * C : 0; break;
-        case 15: src = h->cg.r[0]; n = C * D; break;
-        // 16/17 E slot 0/1 padded to whole blocks [ldE][ldE] (E^-1 once the slot's inversion has run)
-        case 16: case 17: src = h->Ebuf[which - 16]; n = h->tlon ? (size_t)h->tl.ldE * h->tl.ldE : 0; break;
-        default: return INSFM_BA_EINVAL;
-    }
-    if (int rc0 = side_flush(h)) return rc0;
-    if (int rc0 = lin_join(h)) return rc0;
-    if (n) HIPCHK(hipMemcpyAsync(host, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return (int64_t)n;
 }
 
 // ---- global positioning (include/insfm_gp.h) -------------------------------------------------------------------
@@ -3391,25 +1843,6 @@ int insfm_gp_cost(insfm_ba* h, const double* pos, const double* pts, const doubl
     return INSFM_BA_OK;
 }
 
-int insfm_gp_debug_linearize(insfm_ba* h, const double* pos, const double* pts, const double* scales) {
-    if (!h || !pos || !pts || !scales || h->kind != 1) return INSFM_BA_EINVAL;
-    h->keep_S = 1;
-    int rc = gp_io(h, 1, pos, pts, scales);
-    if (rc) return rc;
-    if ((rc = run_linearize(h, h->cams_cur, h->pts_cur))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-int64_t insfm_gp_debug_get_ds(insfm_ba* h, double* host_out) {
-    if (!h || !host_out || h->kind != 1) return INSFM_BA_EINVAL;
-    std::vector<double> loc(h->Nl);
-    if (h->Nl) HIPCHK(hipMemcpyAsync(loc.data(), h->ds, sizeof(double) * h->Nl, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    std::memset(host_out, 0, sizeof(double) * (size_t)h->N);
-    for (int o = 0; o < h->Nl; ++o) host_out[h->osrc_host[o]] = loc[o];
-    return h->N;
-}
-
 }  // extern "C"
 
+#include "ba_debug_api.h"

@@ -1,4 +1,4 @@
-// Host poll policy of the two-level CG (ba_kernels.hip run_solve): no stream sync inside the CG.  The lead workgroup
+// Host poll policy of the two-level CG (ba_solve.h run_tl_cg): no stream sync inside the CG.  The lead workgroup
 // of k_tl_pc publishes {iterations started, status} into host-mapped memory; the host keeps about `ahead` iterations
 // queued, one at a time, and stops when the status word turns non-zero.  Plain C++ (no HIP types) so the policy,
 // including its deadline, is unit-tested on the CPU (tests/test_cg_poll.py builds tests/cpp/cg_poll_test.cpp).
@@ -103,6 +103,49 @@ int cg_poll(CgPoll& s, int limit, int ahead, double stall_s, Status status, Reac
             Query query, Now now, Pause pause, int* rc) {
     return cg_poll(s, limit, ahead, stall_s, stall_s, status, reached, enqueue, query, now, pause, [] { return true; },
                    rc);
+}
+
+// The process's stall limit: INSFM_CG_STALL_S, read once (the CG poll and the cost's publish wait share it).
+inline double cg_stall_limit() {
+    static const double v = cg_stall_limit_s(std::getenv("INSFM_CG_STALL_S"));
+    return v;
+}
+
+// The wait for a trial cost: k_publish writes its result block and then the sequence word `seq` into host-mapped
+// memory.  Bounded like the CG poll: a device that neither publishes nor reports an error ends the wait (kStalled)
+// after limit_s seconds (the caller passes six stall limits).
+// word(): an acquire load of the sequence word;  query(), now(), pause(): as for cg_poll
+struct PublishWait {
+    enum Result { kPublished = 0, kStreamError = -1, kDrainedUnpublished = -2, kStalled = -3 };
+    double stalled_s = 0.0;  // wall-clock seconds waited when the wait gave up
+};
+
+// Sequence words count up from 1 and skip 0 (the word's initial value) when they wrap.
+inline unsigned next_pub_seq(unsigned seq) { return ++seq == 0 ? 1u : seq; }
+
+template <class Word, class Query, class Now, class Pause>
+int publish_wait(PublishWait& s, unsigned seq, double limit_s, Word word, Query query, Now now, Pause pause) {
+    const double t_wait = now();
+    for (unsigned n = 1;; ++n) {
+        if (word() == seq) return PublishWait::kPublished;
+        if ((n & 255) == 0) {
+            const int q = query();
+            if (q < 0) return PublishWait::kStreamError;
+            if (q == 0 && word() != seq) return PublishWait::kDrainedUnpublished;
+            const double dt = now() - t_wait;
+            if (dt > limit_s) {
+                s.stalled_s = dt;
+                return PublishWait::kStalled;
+            }
+        }
+        pause();
+    }
+}
+
+inline void cpu_relax() {  // the spin loops' pause()
+#if defined(__x86_64__)
+    __builtin_ia32_pause();
+#endif
 }
 
 inline double wall_seconds() {

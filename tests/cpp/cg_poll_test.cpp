@@ -112,5 +112,25 @@ int main() {
     }
     std::printf("limit default=%.1f env=%.2f bad=%.1f gate=%.1f\n", cg_stall_limit_s(nullptr), cg_stall_limit_s("0.25"),
                 cg_stall_limit_s("x"), cg_gate_limit_s(10.0));
+    // publish_wait: the sequence word turns `seq` after `publish_at` loads (never if negative); the stream query
+    // answers `query_result`; the fake clock advances one exact tick per now() (one per query, every 256 spins)
+    const double tick = 3.0 / 32768.0;
+    auto wait = [&](const char* name, long publish_at, int query_result, double limit_s) {
+        PublishWait s;
+        long loads = 0, queries = 0;
+        double fake_t = 0.0;
+        const unsigned seq = 7;
+        const int r = publish_wait(
+            s, seq, limit_s, [&] { return ++loads >= publish_at && publish_at >= 0 ? seq : seq - 1; },
+            [&] { ++queries; return query_result; }, [&] { fake_t += tick; return fake_t; }, [] {});
+        std::printf("%s result=%d loads=%ld queries=%ld stalled_s=%.9f\n", name, r, loads, queries, s.stalled_s);
+    };
+    wait("pub_ok", 1000, 1, 0.5);
+    wait("pub_first_poll", 1, 1, 0.5);
+    wait("pub_stream_error", -1, -1, 0.5);
+    wait("pub_drained", -1, 0, 0.5);
+    wait("pub_stalled", -1, 1, 0.5);
+    std::printf("pub_seq wrap=%u zero=%u five=%u tick=%.9f\n", next_pub_seq(0xffffffffu), next_pub_seq(0u),
+                next_pub_seq(5u), tick);
     return 0;
 }

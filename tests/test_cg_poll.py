@@ -1,6 +1,7 @@
-"""CPU unit test of the two-level CG host poll policy (instantsfm_amd/csrc/cg_poll.h, used by ba_kernels.hip
-run_solve): progress, convergence, the launch limit, stream errors, and the wall-clock stall deadline that turns a
-CG launch that never publishes into INSFM_BA_EHIP instead of an endless spin."""
+"""CPU unit test of the two-level CG host poll policy (instantsfm_amd/csrc/cg_poll.h, used by ba_solve.h run_tl_cg):
+progress, convergence, the launch limit, stream errors, and the wall-clock stall deadline that turns a CG launch that
+never publishes into INSFM_BA_EHIP instead of an endless spin; and the bounded wait for a trial cost (publish_wait,
+used by ba_step.h finish_cost)."""
 import os
 import re
 import shutil
@@ -59,6 +60,35 @@ def test_deadline_starts_after_the_gate(poll_out):
     assert float(g["opened"]) >= 2.0
     assert 0.5 <= float(g["stalled_s"]) < 0.6
     assert float(g["end"]) >= 2.5
+
+
+def test_publish_wait_sees_the_word(poll_out):
+    """The wait for a trial cost (publish_wait): done at the load that sees the sequence word, a stream query every
+    256 spins."""
+    ok = poll_out["pub_ok"]
+    assert int(ok["result"]) == 0 and int(ok["loads"]) == 1000 and int(ok["queries"]) == 3
+    first = poll_out["pub_first_poll"]
+    assert int(first["result"]) == 0 and int(first["loads"]) == 1 and int(first["queries"]) == 0
+
+
+def test_publish_wait_errors(poll_out):
+    e = poll_out["pub_stream_error"]
+    assert int(e["result"]) == -1 and int(e["queries"]) == 1  # the first query
+    d = poll_out["pub_drained"]
+    assert int(d["result"]) == -2 and int(d["queries"]) == 1
+    assert int(d["loads"]) == 257  # (the word is read once more after the stream drained)
+
+
+def test_publish_wait_stalls_out(poll_out):
+    """Never published, stream busy: the wait ends within one query interval of the fake clock past the limit."""
+    s, tick = poll_out["pub_stalled"], float(poll_out["pub_seq"]["tick"])
+    assert int(s["result"]) == -3
+    assert 0.5 <= float(s["stalled_s"]) < 0.5 + tick
+
+
+def test_publish_sequence_skips_zero(poll_out):
+    q = poll_out["pub_seq"]
+    assert int(q["wrap"]) == 1 and int(q["zero"]) == 1 and int(q["five"]) == 6
 
 
 def test_gate_that_never_opens_ends_the_poll(poll_out):
