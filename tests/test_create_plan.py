@@ -11,6 +11,7 @@ import types
 import numpy as np
 import pytest
 
+import ragged_scene as RS
 from instantsfm_amd.shard import shard_ranges
 from instantsfm_amd.synth import make_problem
 from oracle import oracle as O
@@ -62,10 +63,18 @@ def _scenes():
         pt = np.repeat(np.arange(600), L)
         cam = (pt % (30 - L + 1)) + np.tile(np.arange(L)[::-1], 600)
         out[name] = _scene(types.SimpleNamespace(n_cams=30, n_points=600, model=2), cam, pt, K=4)
+    # ragged scenes (tests/ragged_scene.py; the GPU runs them in test_gpu_ragged.py) at the product's cluster target:
+    # tracks of 2..275 observations, duplicates, a camera that sees nothing and rows of ~269 upper blocks (dense, in
+    # the atomic and the deterministic form of the Schur limits); tracks inside a window of 61 cameras (banded)
+    dense = RS.dense_problem(2)
+    out["ragged_dense"] = _scene(dense, K=24, oracle=True)
+    out["ragged_dense_det"] = _scene(dense, K=24, det=True)
+    out["ragged_banded"] = _scene(RS.banded_problem(2), K=24, oracle=True)
     return out
 
 
 NAMES = sorted(["one_cluster", "duplicates", "empty_camera", "shard_empty", "band_padded", "band_unpadded",
+                "ragged_dense", "ragged_dense_det", "ragged_banded",
                 *(f"clusters_K{K}{p}" for K in (4, 16, 32) for p in ("", "_perm")), *(f"model6_K{K}" for K in (2, 3)),
                 *(f"shard_{r}_of_{w}" for w in (2, 4) for r in range(w))])
 
@@ -96,6 +105,13 @@ def _limits(sc, C, D):
     if sc["tight_lds"]:  # room for 10 blocks only: long rows are split
         budget = target = 8 * (D + 12) + 4 * C + 8 * waves * (64 // D) * ws + 64 + 8 * bs * 10 + 8
     return budget, target, waves, ws, bs
+
+
+def schur_cap(limits, C, D):
+    """blocks per Schur row chunk (create_plan.h plan_schur_work) under _limits' (budget, target, waves, ws, bs)"""
+    _, target, waves, ws, _bs = limits
+    fixed = 8 * (D + 12) + 4 * C + 8 * waves * (64 // D) * ws + 64
+    return (target - fixed) // (8 * _bs)
 
 
 @pytest.fixture(scope="module")
@@ -277,6 +293,8 @@ def test_neighbour_lists(plan, name):
     assert pl["nb"] == (64 if pl["maxlen"] <= 64 else 128 if pl["maxlen"] <= 128 else 0)
     assert pl["nb_wide"] == (128 if pl["maxlen"] <= 128 else 0)
     assert pl["cgp_ok"] == int(pl["nb"] > 0 and pl["maxseg"] <= SEG_MAX)
+    if name.startswith("ragged_"):  # dense: launch-path CG; banded: rows of 65..128 neighbours on the persistent CG
+        assert (pl["nb"], pl["cgp_ok"]) == ((128, 1) if name == "ragged_banded" else (0, 0))
     # slot source list of k_tl_cgp
     src = pl["src"]
     assert np.array_equal(src[pup[e]], e) and np.array_equal(src[plo[e]], ~e)
@@ -299,11 +317,15 @@ def test_schur_work_and_exchange_chunks(plan, name):
     assert np.array_equal(kb[first], rptr[:-1]) and np.array_equal(ke[last], rptr[1:])
     assert np.all(kb[1:][~first[1:]] == ke[:-1][~first[1:]]) and np.all(ke > kb)
     fixed = 8 * (D + 12) + 4 * C + 8 * waves * (64 // D) * ws + 64
-    assert pl["cap"] == (target - fixed) // (8 * bs)
+    assert pl["cap"] == (target - fixed) // (8 * bs) == schur_cap(pl["limits"], C, D)
     assert np.all(ke - kb <= pl["cap"]) and pl["max_chunk"] == (ke - kb).max()
     assert pl["schur_lds"] <= budget and pl["schur_lds"] % 16 == 0
     if sc["tight_lds"]:
         assert pl["cap"] == 10 and row.size > C  # long rows were split
+    if name.startswith("ragged_dense"):  # at the shipped limits: nearly every row is longer than a chunk
+        assert not sc["tight_lds"] and np.diff(rptr).max() - 1 > pl["cap"] and row.size > C
+        assert np.count_nonzero(np.bincount(row, minlength=C) > 1) > C // 3
+        assert np.bincount(row, minlength=C)[7] == 1  # the camera that sees nothing: one item, its diagonal block
     xr, xw = pl["xr"], pl["xw"]
     assert xr.size == xw.size <= X_CHUNKS + 1
     assert xr[0] == 0 and xr[-1] == C and np.all(np.diff(xr) > 0)
@@ -321,6 +343,13 @@ def test_linearize_runs(plan, name):
     assert lb[0] == 0 and lb[-1] == Pl and np.all(np.diff(lb) > 0)
     tracks, obs = np.diff(lb), lptr[lb[1:]] - lptr[lb[:-1]]
     assert np.all(tracks <= LIN_THREADS) and np.all((obs <= LIN_THREADS) | (tracks == 1))
+    if name.startswith("ragged_dense"):
+        assert np.any((tracks == 1) & (obs > LIN_THREADS)) and np.any((tracks == 1) & (obs > 2 * LIN_THREADS))
+        # a run closed by the observation limit: the next track would not have fitted, the track limit was not reached
+        nxt = lptr[lb[1:-1] + 1] - lptr[lb[1:-1]]
+        assert np.any((tracks[:-1] < LIN_THREADS) & (tracks[:-1] > 1) & (obs[:-1] + nxt > LIN_THREADS))
+    if name == "ragged_banded":  # unequal tracks: no run reaches the track limit, every run is closed by observations
+        assert np.all(tracks < LIN_THREADS) and np.unique(tracks).size > 3
 
 
 @pytest.mark.parametrize("name", NAMES)
