@@ -29,7 +29,7 @@
 // parity buffer before the grid barrier, and after it every workgroup sums each cluster's runs itself in run order
 // (det_cluster_sums).  Either variant applies the coarse correction additively (precond 1) or as A-DEF2 (ADEF,
 // precond 2; round 6 added the DET form of A-DEF2, so the multi-rank and deterministic paths run it too).
-// Host eligibility (ba_kernels.hip, create): D = 8, host-mapped progress word, rows of at most NB = 128 blocks stored in
+// Host eligibility (ba_create.h): D = 8, host-mapped progress word, rows of at most NB = 128 blocks stored in
 // cluster order (tl.sperm the identity), at most kCgpSegMax neighbour clusters per row, and every workgroup resident at
 // once (one per CU) -- for ranks sharing a GPU, all of their grids at once.
 #pragma once
@@ -426,7 +426,7 @@ __global__ __launch_bounds__(kCgpThreads, 1) void k_tl_cgp(int C, const int* __r
     if (lane == 0) pcl[rl] = has_row ? ci : -1;
     const bool use = tl.ok[0] != 0;
     // R(r0) into rs: the cluster sums of k_cg_factor_basis's run partials (parity-1 run records, slots 3..11, summed in
-    // run order), or with oseg bit 3 k_tl_basis's per-cluster sums tl.Rc (the separate launches; FACTOR_BASIS=0)
+    // run order), or with oseg bit 3 k_tl_basis's per-cluster sums tl.Rc (the separate k_cg_factor and k_tl_basis launches)
     auto r0_restriction = [&]() {
         if (oseg & 8) {
             for (int q = t; q < m; q += kCgpThreads) rs[q] = tl.Rc[q];

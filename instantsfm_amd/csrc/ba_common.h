@@ -1,4 +1,4 @@
-// Shared definitions of the BA kernels (ba_kernels.hip, ba_twolevel.h, tools/bench_dense.hip).
+// Shared definitions of the BA kernels (ba_kernels.hip and its headers, tools/bench_dense.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,35 @@ __device__ __forceinline__ void wave_sum3(double& a, double& b, double& c) {
         b += tb;
         c += tc;
     }
+}
+
+__device__ __forceinline__ double readlane_d(double v, int lane) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+
+// Fixed-order block reduction of NV values per thread, returned to every thread: a butterfly per wave, then the wave
+// sums in wave order (one barrier instead of one per tree level).  (ba_gp.h's block_sum, over a [waves][NV] buffer,
+// gives thread 0 alone the result.)
+template <int NV, int NT = kThreads>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double* sh /* >= NV * NT / 64 doubles */) {
+    constexpr int NW = NT / 64;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane == 0) sh[k * NW + wv] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        double s = sh[k * NW];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) s += sh[k * NW + w];
+        v[k] = s;
+    }
+    __syncthreads();
 }
 
 

@@ -219,6 +219,12 @@ __device__ __forceinline__ void retract_pose(const double* x, const double* d, d
     out[6] = qdw * bw - qdx * bx - qdy * by - qdz * bz;
 }
 
+__device__ __forceinline__ double huber_weight_sqrt(double s, double delta) {
+    const double rs = sqrt(s);
+    const double w = rs < delta ? 1.0 : delta / rs;
+    return sqrt(w);
+}
+
 __device__ __forceinline__ double clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // Inverse of an SPD 3x3 given as [xx, xy, xz, yy, yz, zz] via Cholesky (same operation order as the oracle).

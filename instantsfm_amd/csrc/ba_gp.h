@@ -121,7 +121,7 @@ __device__ __forceinline__ void group_sum(double (&v)[NV]) {
 }
 
 // A group of G lanes per local track (CSR-vector): lane l takes observations ob + l, ob + l + G, ... so a group reads
-// G consecutive 64-byte records per round.  Scale-eliminated W_o (as {u, beta^2}, see load_wcol in ba_kernels.hip),
+// G consecutive 64-byte records per round.  Scale-eliminated W_o (as {u, beta^2}, see load_wcol in ba_schur.h),
 // damped V_p (packed), g'_p, V^-1, y.
 template <int G>
 __global__ __launch_bounds__(kThreads) void k_gp_prep_points(int Pl, const int* __restrict__ pt_ptr, const double* __restrict__ gobs,

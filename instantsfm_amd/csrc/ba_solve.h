@@ -97,19 +97,18 @@ void launch_lin_points_w(insfm_ba* h, const double* cams, const double* pts_loca
                                                          pp1, stamp_ptr(h, kStLinPoints));
 }
 
-// k_lin_cams on `stream`: the register form up to D = 9, else the LDS form (no `else`: the LDS form stays instantiated
-// for every model, so the set of device kernels is what it was).
+// k_lin_cams on `stream`: the register form up to D = 9, else the LDS form.
 template <int M>
 void launch_lin_cams(insfm_ba* h, hipStream_t stream, const double* cams, const double* pts_local) {
     constexpr int D = kD<M>;
     if constexpr (D <= 9) {
         k_lin_cams_reg<M><<<h->C, LIN_CAMS_NT, 0, stream>>>(h->cam_ptr, h->cm_pt, h->cm_uv, h->pp, cams, pts_local,
                                                          h->d.huber_delta, h->U, h->gc);
-        return;
+    } else {
+        const size_t lds = sizeof(double) * kThreads * (2 * D + 2);
+        k_lin_cams<M><<<h->C, kThreads, lds, stream>>>(h->cam_ptr, h->cm_pt, h->cm_uv, h->pp, cams, pts_local,
+                                                       h->d.huber_delta, h->U, h->gc);
     }
-    const size_t lds = sizeof(double) * kThreads * (2 * D + 2);
-    k_lin_cams<M><<<h->C, kThreads, lds, stream>>>(h->cam_ptr, h->cm_pt, h->cm_uv, h->pp, cams, pts_local,
-                                                   h->d.huber_delta, h->U, h->gc);
 }
 
 int run_linearize(insfm_ba* h, const double* cams, const double* pts_local) {
@@ -811,7 +810,7 @@ int run_solve(insfm_ba* h, double f, const double* cams, const double* pts_local
         // linearization that factorizes its own E (k_tl_erow reads Sn), the launch-path CG and the debug getters do
         const bool scale = !(h->tlon && h->cgp_nb && h->tl_solves > 0 && h->tl_fresh && !h->keep_S);
         // the persistent CG's solves: the factorization and the coarse basis in one launch (k_cg_factor_basis)
-        h->basis_by_factor = FACTOR_BASIS && h->tlon && h->cgp_nb && !gpk;
+        h->basis_by_factor = h->tlon && h->cgp_nb && !gpk;
         rc = with_D(D, [&](auto dc_) -> int {
             constexpr int DV = decltype(dc_)::value;
             launch_factor<DV>(h, f, ul, cams, true);

@@ -36,7 +36,8 @@ int cgp_collective_fallback(insfm_ba* h, int st0) {
 }
 
 // The persistent CG's factorization and coarse basis again on the completed S / b (no U / g_c added: the same L,
-// L^-1 and r0 = L^-1 b): k_cg_factor_basis, or (FACTOR_BASIS=0 builds) k_cg_factor and k_tl_basis.
+// L^-1 and r0 = L^-1 b): k_cg_factor_basis, or (a handle whose solves did not form the basis there) k_cg_factor and
+// k_tl_basis.
 int refactor_for_cgp(insfm_ba* h, const double* cams) {
     const int rc = with_D(h->D, [&](auto dc_) -> int {
         launch_factor<decltype(dc_)::value>(h, 1.0, false, cams);

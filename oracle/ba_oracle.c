@@ -884,7 +884,7 @@ static void tri_inv(int n, const double* L, double* Li) {
 }
 
 /* E^-1 in place by blocked Gauss-Jordan inversion, 32-wide blocks (the last one partial), the GPU's algorithm
- * (csrc/ba_twolevel.h k_gj_pinv0 / k_gj_step) with its fused multiply-adds -- the pivot update a - aip * rpc as
+ * (csrc/ba_gj.h k_gj_pinv0 / k_gj_step) with its fused multiply-adds -- the pivot update a - aip * rpc as
  * fma(-aip, rpc, a), every tile product as one fma chain in k order (v_mfma_f64_16x16x4f64 accumulates like that) --
  * so the two round alike: per block step k with pivot block P = A_kk
  *   P^-1 by scalar in-place Gauss-Jordan (pivots in order), A_kj <- P^-1 A_kj, A_ij <- A_ij - A_ik A_kj (new A_kj),

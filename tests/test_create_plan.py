@@ -18,7 +18,7 @@ from oracle import oracle as O
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_NI = {0: 1, 1: 2, 2: 2, 3: 3, 4: 6, 5: 6, 6: 10, 8: 2, 9: 3}
-# the device-side constants create passes to the plan (ba_kernels.hip, ba_twolevel.h, ba_cgp.h); the properties below
+# the device-side constants create passes to the plan (ba_schur.h, ba_lin.h, ba_twolevel.h, ba_cgp.h); the properties below
 # hold for any values
 LDS_BUDGET, LDS_TARGET, LDS_TARGET_DET = 96 * 1024, 96 * 1024, 52 * 1024
 SCHUR_WAVES, DET_WAVES, SCHUR_CHUNK = 8, 4, 4

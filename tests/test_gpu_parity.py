@@ -65,7 +65,7 @@ def test_linearize_parity(model):
     eng.debug_linearize(dev(prob.cams_init), dev(prob.points_init))
     ora.linearize(prob.cams_init, prob.points_init)
     N, P, C, D = prob.n_obs, prob.n_points, prob.n_cams, eng.D
-    # the stored records are the symmetric Y_o = W_o L_p (PointPrep in csrc/ba_kernels.hip): L_p = R_p^-T with R_p the
+    # the stored records are the symmetric Y_o = W_o L_p (PointPrep in csrc/ba_lin.h): L_p = R_p^-T with R_p the
     # Cholesky factor of the point block damped for the first trial (f = 1 + damping = 1 + 1e-4), stored [o][3][D]
     assert rel(eng.debug_get(0, (N, 3, D)).transpose(0, 2, 1), y_records(ora, prob.pt_idx, 1.0 + 1e-4)) < 1e-12
     assert rel(eng.debug_get(1, (P, 6)), ora.get(O.V)) < 1e-12

@@ -11,7 +11,7 @@
 #include <random>
 #include <vector>
 
-#include "../instantsfm_amd/csrc/ba_twolevel.h"
+#include "../instantsfm_amd/csrc/ba_gj.h"
 
 using namespace insfm;
 

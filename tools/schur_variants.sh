@@ -1,6 +1,7 @@
 #!/usr/bin/env bash
-# Compile variants of the HIP library with different k_schur tuning macros into tools/lib_<name>.so (CPU, in this
-# container); tools/schur_probe.py times k_schur for each on the GPU.  usage: tools/schur_variants.sh name:"-DX=1 ..." ...
+# Compile variants of the HIP library that override k_schur's numeric knobs (csrc/ba_schur.h: SCHUR_LDS_KB, SCHUR_UP,
+# INSFM_SCHUR_WAVES, ...) into tools/lib_<name>.so (CPU, in this container); tools/schur_probe.py times k_schur for each
+# on the GPU.  usage: tools/schur_variants.sh name:"-DSCHUR_UP=8 ..." ...
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p build/variants
