@@ -37,6 +37,7 @@
 
 #include "ba_common.h"
 #include "ba_twolevel.h"
+#include "solve_policy.h"
 
 namespace insfm {
 
@@ -223,7 +224,8 @@ __device__ __forceinline__ void det_cluster_sums(const double* rb, int off, cons
 // NB: blocks per row held in registers (a multiple of 8).  wx: [2][C][8] the w exchange by iteration parity (a
 // workgroup's P2 may run while another is still gathering in P1); yg: [m][2] the tagged granules of y, tag0 the tag of
 // iteration 0 (tags never repeat on a handle); sync: kCgpSyncWords barrier words, epoch0: the barriers they have
-// counted so far (one per iteration of earlier launches); oseg bit 0: also write this solve's coarse segments tl.Oseg
+// counted so far (one per iteration of earlier launches); oseg: the CgpFlag bits of solve_policy.h -- bit 0: also write
+// this solve's coarse segments tl.Oseg
 // (the E build behind the CG then skips k_tl_erow), bit 1 (tests, INSFM_DIAG=cgp_fault): the last workgroup leaves
 // at iteration 2 as if a barrier had timed out, bit 2 (tests, INSFM_DIAG=adef2_breakdown): an A-DEF2 launch reports a
 // breakdown (status 2) at iteration 2, bit 3: the restriction of r0 comes from k_tl_basis (tl.Rc) instead of
@@ -428,7 +430,7 @@ __global__ __launch_bounds__(kCgpThreads, 1) void k_tl_cgp(int C, const int* __r
     // R(r0) into rs: the cluster sums of k_cg_factor_basis's run partials (parity-1 run records, slots 3..11, summed in
     // run order), or with oseg bit 3 k_tl_basis's per-cluster sums tl.Rc (the separate k_cg_factor and k_tl_basis launches)
     auto r0_restriction = [&]() {
-        if (oseg & 8) {
+        if (oseg & kCgpRestrictionFromBasis) {
             for (int q = t; q < m; q += kCgpThreads) rs[q] = tl.Rc[q];
         } else {
             det_cluster_sums<MC>(runs + (size_t)gridDim.x * kCgpRows * 12, 3, clp, nc, rs);
@@ -443,7 +445,7 @@ __global__ __launch_bounds__(kCgpThreads, 1) void k_tl_cgp(int C, const int* __r
     if (trace && blockIdx.x == 0 && t == 0) trace[579] = (double)wall_clock64();  // (A_ic complete)
     // the coarse matrix's row segments of this solve for the E build that runs behind the CG (k_tl_erow's outputs:
     // Z~_i^T A_ic, plus Z~_i^T Z~_i on the own-cluster segment, in k_tl_erow's order of additions)
-    if ((oseg & 1) && has_row) {
+    if ((oseg & kCgpWriteSegments) && has_row) {
         const int ns = min(nseg, kCgpSegMax);
         for (int sg = 0; sg < ns; ++sg) {
             const int own_seg = tl.seg[s0 + sg].w;
@@ -853,7 +855,7 @@ __global__ __launch_bounds__(kCgpThreads, 1) void k_tl_cgp(int C, const int* __r
         trace[257] = (double)wall_clock64();
     }
     for (; alive; ++it) {
-        if ((oseg & 2) && it == 2 && blockIdx.x == gridDim.x - 1) {  // (fault injection: see above)
+        if ((oseg & kCgpTestFault) && it == 2 && blockIdx.x == gridDim.x - 1) {  // (fault injection: see above)
             if (t == 0) __hip_atomic_store(cgp_abort(sync), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             alive = false;
             break;
@@ -921,7 +923,7 @@ __global__ __launch_bounds__(kCgpThreads, 1) void k_tl_cgp(int C, const int* __r
             const double den = (it == 0) ? del : del - be * gam / h_alpha;
             if (!(den > 0.0)) done = 2;
             else alpha = gam / den;
-            if (ADEF && (oseg & 4) && it == 2) done = 2;  // (INSFM_DIAG=adef2_breakdown: a breakdown, for the tests)
+            if (ADEF && (oseg & kCgpTestBreakdown) && it == 2) done = 2;  // (INSFM_DIAG=adef2_breakdown: a breakdown, for the tests)
         }
         if (trace && blockIdx.x == 0 && t == 0 && it < 64) {  // INSFM_DIAG=cgp_trace
             trace[4 * it] = gam; trace[4 * it + 1] = del; trace[4 * it + 2] = rho; trace[4 * it + 3] = done;

@@ -380,27 +380,14 @@ int setup_host_sync(insfm_ba* h) {
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) return create_err(h, INSFM_BA_EHIP, std::string("init: ") + hipGetErrorString(e));
     }
-    // the Schur kernels may need more than the default dynamic-LDS limit
-    with_D(h->D, [&](auto dc_) -> int {
-        constexpr int DV = decltype(dc_)::value;
-        (void)hipFuncSetAttribute((const void*)k_schur<DV, kDetWaves, false, false, SCHUR_DET_ORD>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->schur_lds);
-        (void)hipFuncSetAttribute((const void*)k_schur<DV, kSchurWaves>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    // the Schur kernels this handle launches (first trial, retried trial) may need more than the default dynamic-LDS limit
+    const bool det = h->d.deterministic != 0;
+    for (const bool retry : {false, true})
+        if (const SchurKernel k = schur_kernel(h->kind, h->D, det, retry))
+            (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->schur_lds);
+    if (h->kind == 1 && !det)
+        (void)hipFuncSetAttribute((const void*)k_schur_gp<kSchurWaves, kGPSG>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)h->schur_lds);
-        (void)hipFuncSetAttribute((const void*)k_schur<DV, kDetWaves, false, true, SCHUR_DET_ORD>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->schur_lds);
-        (void)hipFuncSetAttribute((const void*)k_schur<DV, kSchurWaves, false, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->schur_lds);
-        if constexpr (DV == 3) {
-            (void)hipFuncSetAttribute((const void*)k_schur<3, kDetWaves, true, false, SCHUR_DET_ORD>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->schur_lds);
-            (void)hipFuncSetAttribute((const void*)k_schur<3, kSchurWaves, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)h->schur_lds);
-            (void)hipFuncSetAttribute((const void*)k_schur_gp<kSchurWaves, kGPSG>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)h->schur_lds);
-        }
-        return 0;
-    });
     return 0;
 }
 

@@ -104,12 +104,12 @@ int insfm_ba_cg_attach(insfm_ba* h, const void* handles) {
 
 int insfm_ba_debug_time_xchg(insfm_ba* h, int32_t reps, double* us) {
     if (!h || !us || !h->xpart || reps < 1) return INSFM_BA_EINVAL;
-    HIPCHK(hipEventRecord(h->ev[10], h->stream));
+    HIPCHK(hipEventRecord(h->ev[kEvDebug], h->stream));
     for (int r = 0; r < reps; ++r) launch_xchg(h, 1);  // (slot 1: not gated by the CG status)
-    HIPCHK(hipEventRecord(h->ev[11], h->stream));
-    HIPCHK(hipEventSynchronize(h->ev[11]));
+    HIPCHK(hipEventRecord(h->ev[kEvDebugEnd], h->stream));
+    HIPCHK(hipEventSynchronize(h->ev[kEvDebugEnd]));
     float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[10], h->ev[11]));
+    HIPCHK(hipEventElapsedTime(&ms, h->ev[kEvDebug], h->ev[kEvDebugEnd]));
     *us = 1e3 * ms / reps;
     return INSFM_BA_OK;
 }
@@ -141,7 +141,7 @@ int insfm_ba_debug_solve(insfm_ba* h, double f) {
     cgp_drop_pending(h);
     h->keep_S = 1;
     // solves around the parameters last passed to insfm_ba_debug_linearize
-    int it = run_solve(h, f, h->cams_cur, h->pts_cur);
+    int it = run_solve(h, f, h->cams_cur, h->pts_cur, false);
     HIPCHK(hipStreamSynchronize(h->stream));
     return it;
 }
@@ -214,21 +214,18 @@ int insfm_ba_debug_time_kernel(insfm_ba* h, int32_t which, int32_t reps, double*
         HIPCHK(hipMemsetAsync(h->tl.Racc + h->tl.m, 0, sizeof(double) * h->tl.m, h->stream));
         HIPCHK(hipMemsetAsync(h->tl.Gacc + 3 * h->tl.nc, 0, sizeof(double) * 3 * h->tl.nc, h->stream));
         with_D(h->D, [&](auto dc_) -> int {
-            constexpr int DV = decltype(dc_)::value;
-            k_tl_pspmv<DV><<<h->C, kPspmvThreads, 0, h->stream>>>(0, h->C, h->nbr_stride, h->nbr_ptr, h->nbr_j, h->Sn,
-                                                                 h->Lf, h->cg, h->tl, XPart{});
+            launch_pspmv<decltype(dc_)::value>(h, 0, h->C, h->tl);
             return 0;
         });
     }
-    HIPCHK(hipEventRecord(h->ev[10], h->stream));
+    HIPCHK(hipEventRecord(h->ev[kEvDebug], h->stream));
     int rc = with_D(h->D, [&](auto dc_) -> int {
         constexpr int DV = decltype(dc_)::value;
         for (int r = 0; r < reps; ++r) {
             if (which == 2) {
                 launch_tl_iter<DV>(h, 1, h->d.pcg_max_iter, 0.0);
             } else if (which == 3) {
-                k_tl_pspmv<DV><<<h->C, kPspmvThreads, 0, h->stream>>>(1, h->C, h->nbr_stride, h->nbr_ptr, h->nbr_j, h->Sn, h->Lf, h->cg,
-                                                                   h->tl, XPart{});
+                launch_pspmv<DV>(h, 1, h->C, h->tl);
             } else if (which == 4) {
                 int rc2 = run_tl_basis(h, h->cams_cur, h->stream);
                 if (!rc2) rc2 = run_tl_build(h, 0, h->stream);
@@ -249,19 +246,18 @@ int insfm_ba_debug_time_kernel(insfm_ba* h, int32_t which, int32_t reps, double*
                 k_cg_iter<DV><<<h->C, kCgThreads, 0, h->stream>>>(1, h->C, h->d.pcg_max_iter, 0.0, h->nbr_ptr, h->nbr_j, h->Sn,
                                                                 h->Lf, h->cg);
             else {  // the k_schur form this handle runs (deterministic mode: one wave per workgroup, its LDS layout)
-                const int rc2 = launch_schur(h, h->kind ? h->Up : h->U, h->kind ? h->gpc : h->gc, 1.0,
-                                             h->kind ? -1e308 : h->d.clamp_min, h->kind ? 1e308 : h->d.clamp_max,
-                                             h->kind ? 1 : h->d.rank == 0, false);
+                const int rc2 = launch_schur(h, 1.0, h->kind ? -1e308 : h->d.clamp_min,
+                                             h->kind ? 1e308 : h->d.clamp_max, h->kind ? 1 : h->d.rank == 0, false);
                 if (rc2) return rc2;
             }
         }
         return launch_err(h, "debug_time_kernel");
     });
     if (rc) return rc;
-    HIPCHK(hipEventRecord(h->ev[11], h->stream));
-    HIPCHK(hipEventSynchronize(h->ev[11]));
+    HIPCHK(hipEventRecord(h->ev[kEvDebugEnd], h->stream));
+    HIPCHK(hipEventSynchronize(h->ev[kEvDebugEnd]));
     float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[10], h->ev[11]));
+    HIPCHK(hipEventElapsedTime(&ms, h->ev[kEvDebug], h->ev[kEvDebugEnd]));
     *us_per_launch = 1e3 * ms / reps;
     return INSFM_BA_OK;
 }
@@ -276,30 +272,29 @@ int insfm_ba_debug_time_cgp(insfm_ba* h, int32_t reps, double* out) {
     cgp_drop_pending(h);
     if (int rc0 = side_flush(h)) return rc0;
     if (int rc0 = lin_join(h)) return rc0;
-    const int maxit = h->d.pcg_max_iter;
-    const double tol2 = h->d.pcg_tol * h->d.pcg_tol;
     double t_cg = 0.0, t_pc = 0.0, iters = 0.0;
     for (int r = 0; r < reps; ++r) {
         HIPCHK(hipMemsetAsync(h->cg.status, 0, sizeof(int) * 4, h->stream));
-        if (int rc = refactor_for_cgp(h, h->cams_new)) return rc;  // (the last trial's cameras)
+        // (the last trial's cameras; a handle whose solves did not form the basis with the factorization: k_tl_basis)
+        if (int rc = refactor(h, h->last.basis_by_factor ? h->cams_new : nullptr)) return rc;
+        if (!h->last.basis_by_factor)
+            if (int rc = run_tl_basis(h, h->cams_new, h->stream)) return rc;
         volatile int* pg = h->prog_host;
         pg[0] = pg[1] = pg[2] = pg[3] = 0;
         std::atomic_thread_fence(std::memory_order_seq_cst);
-        h->cgp_defer = true;  // (oseg: the segments are written, as in the lagged solves that are most of a run)
-        HIPCHK(hipEventRecord(h->ev[10], h->stream));
-        if (int rc2 = launch_tl_cgp(h, maxit, tol2)) { h->cgp_defer = false; return rc2; }
-        h->cgp_defer = false;
-        h->cgp_tag += (unsigned)maxit + 3u;
-        HIPCHK(hipEventRecord(h->ev[11], h->stream));
-        HIPCHK(hipEventSynchronize(h->ev[11]));
+        HIPCHK(hipEventRecord(h->ev[kEvDebug], h->stream));
+        // (the segments are written, as in the lagged solves that are most of a run)
+        if (int rc2 = launch_tl_cgp(h, h->adef2, true)) return rc2;
+        HIPCHK(hipEventRecord(h->ev[kEvDebugEnd], h->stream));
+        HIPCHK(hipEventSynchronize(h->ev[kEvDebugEnd]));
         int st[3];
-        if (int rc2 = cgp_complete(h, st)) return rc2;
+        if (int rc2 = cgp_complete(h, h->adef2, st)) return rc2;
         if (st[0] != 1) {
             h->err = "debug_time_cgp: the CG ended with status " + std::to_string(st[0]);
             return st[0] == 2 ? INSFM_BA_ESOLVER : INSFM_BA_EHIP;
         }
         float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev[10], h->ev[11]));
+        HIPCHK(hipEventElapsedTime(&ms, h->ev[kEvDebug], h->ev[kEvDebugEnd]));
         t_cg += ms;
         iters += st[1];
     }

@@ -19,6 +19,26 @@
 #include "../../include/insfm_ba.h"
 #include "ba_common.h"
 #include "ba_twolevel.h"
+#include "solve_policy.h"
+
+// What one solve leaves for the next (and for the cost, the repeats and the debug entry points behind it).
+// insfm_ba_reset puts back tl_solves, tl_fresh and last_cg_iters alone.
+struct SolveCarry {
+    long long tl_solves = 0;     // two-level solves so far: its parity is the coarse-inverse slot of the next one
+    bool tl_fresh = false;       // no solve since the last linearization (the lag rule applies to that solve only)
+    bool sn_valid = false;       // Sn holds the scaled S~ of the current solve (k_cg_scale ran for it)
+    bool built_pending = false;  // the side stream's E build may still read S~ / Z~ (the next solve waits for ev_built)
+    bool lin_pending = false;    // k_lin_cams on `aux` has not been joined yet (lin_join waits for ev_lc)
+    bool flags_dirty = false;    // a solve's point preparation ran and no k_final has consumed (cleared) its flag yet
+    bool prep_valid = false;     // the last linearization prepared the points (Vinv, y, status) for damping factor prep_f
+    double prep_f = 0.0;         // (PointPrep)
+    bool chain_oseg = false;     // the side chain of the last solve builds E from k_tl_cgp's segments (reissue_chain)
+    bool cgp_pending = false;    // a k_tl_cgp launch whose status the host has not read yet (cgp_complete)
+    bool cgp_lost = false;       // the last k_tl_cgp timed out at a grid barrier (another process holds CUs)
+    unsigned cgp_epochs = 0;     // grid barriers the counters in cgp_sync have counted (reset with them)
+    unsigned cgp_tag = 1;        // tag of the next k_tl_cgp launch's first iteration
+    int last_cg_iters = 16;      // the last converged CG's iterations (sizes the next CG's first batch)
+};
 
 struct insfm_ba {
     insfm_ba_desc d{};
@@ -40,7 +60,6 @@ struct insfm_ba {
     double* Sn = nullptr;  // row-contiguous scaled neighbour blocks for the CG (both triangles, padded rows)
     int64_t n_nbr = 0;
     int nbr_stride = 0;  // > 0: every CG row has exactly nbr_stride neighbour slots (padded), row r starts at r * stride
-    bool flags_dirty = false;  // a solve's point preparation ran and no k_final has consumed (cleared) its flag yet
     int keep_S = 0;      // debug entry points: every solve forms the scaled copy Sn (insfm_ba_debug_get(5) reads S~ from it;
                          // S itself stays unscaled -- k_tl_cgp reads it)
     std::vector<int> pos_up_host;  // [nnzb] Sn slot of each upper block (debug_get(5))
@@ -69,9 +88,6 @@ struct insfm_ba {
     int* flags = nullptr;
     double* host_res = nullptr;  // pinned 128 B: result[0..4] (doubles) | cg status (ints, from double slot 8)
     int* prog_host = nullptr;    // pinned, device-mapped: progress of the two-level CG (CgBufs::prog)
-    // the last linearization already prepared the points (Vinv, y, status) for damping factor prep_f (PointPrep)
-    bool prep_valid = false;
-    double prep_f = 0.0;
     double* pub_host = nullptr;  // pinned, device-mapped: k_publish's result[0..4], decision, sequence word (double 8)
     double* pub_dev = nullptr;
     unsigned pub_seq = 0;
@@ -79,7 +95,8 @@ struct insfm_ba {
     // LM state
     double damping = 0.0, down = 0.0, loss = 0.0;
     bool have_loss = false;
-    int last_cg_iters = 16;
+    SolveCarry ss;          // solve-to-solve state
+    insfm::SolvePlan last;  // the plan of the last solve (solve_policy.h): the repeats and the debug timers read it
     hipEvent_t ev[18]{};  // 0-9 phase markers, 10-11 debug timing, 12-15 the side chain's start / end by slot,
                           // 16-17 the chunked exchange's span on the exchange stream
     bool chain_timed[2]{};  // set_timing: the side chain of that slot has timing events not yet harvested
@@ -95,25 +112,16 @@ struct insfm_ba {
     size_t pc_lds = 0;
     int pc_rows = 0;  // k_tl_pc rows per restriction pass
     // the register-resident persistent CG (ba_cgp.h k_tl_cgp): blocks per row (0: not eligible), grid, the w exchange
-    // [C][8], the coarse vector [kCoarseMax], the grid-barrier words; cgp_defer: the side chain of slot cgp_slot is
-    // issued behind the CG (k_tl_cgp holds every SIMD of its CUs, so a chain beside it would crawl on the rest)
-    int cgp_nb = 0, cgp_grid = 0, cgp_slot = 0;
+    // [C][8], the coarse vector [kCoarseMax], the grid-barrier words
+    int cgp_nb = 0, cgp_grid = 0;
     bool cgp_det = false;                // fixed-order partial sums (deterministic mode, multi-rank replicated CG)
     bool adef2 = false;                  // precond 2: k_tl_cgp applies the coarse correction as A-DEF2 (ba_cgp.h)
-    bool basis_by_factor = false;        // this solve's coarse basis was formed by k_cg_factor_basis
-    int adef2_fallbacks = 0;             // A-DEF2 solves that broke down and were repeated additively (adef2_fallback)
+    int adef2_fallbacks = 0;             // A-DEF2 solves that broke down and were repeated additively (repeat_trial)
     double* cgp_runs = nullptr;               // [2][grid * 4][12] the cluster runs' partials by parity (cgp_det)
     int* cgp_src = nullptr;     // [n_nbr] S block of each CG slot: e (upper), ~e (lower, transposed), INT_MIN (pad)
-    bool sn_valid = false;      // Sn holds the scaled S~ of the current solve (k_cg_scale ran for it)
     long long* stamps = nullptr;  // INSFM_DIAG=stamps: [kStampSteps][kStKinds][2] kernel entry / exit (wall_clock64)
     long long stamp_step = 0;     // LM steps stamped so far
-    unsigned cgp_epochs = 0;  // grid barriers the counters in cgp_sync have counted (reset with them)
-    bool cgp_defer = false;
     int cgp_slots = 0;            // workgroups of k_tl_cgp the device holds at once
-    bool cg_async = false;        // lm_step: a k_tl_cgp solve's status is read after the trial's k_publish
-    bool cgp_pending = false;     // a k_tl_cgp launch whose status the host has not read yet (cgp_complete)
-    bool dc_by_cgp = false;       // this solve's k_tl_cgp writes dc itself (cg_tail launches no k_cg_finish)
-    bool cgp_lost = false;        // the last k_tl_cgp timed out at a grid barrier (another process holds CUs)
     double* cgp_trace = nullptr;  // INSFM_DIAG=cgp_trace: [64][4] of the last solve, printed to stderr
     // row-partitioned multi-rank CG (ba_xpart.h; insfm_ba_cg_window / insfm_ba_cg_attach)
     bool xpart = false;
@@ -127,9 +135,7 @@ struct insfm_ba {
     std::vector<int> xq;               // [world + 1] cluster-ordered row ranges of the ranks
     double* cgp_wx = nullptr;           // [2][C][8]
     unsigned long long* cgp_yg = nullptr;  // [kCoarseMax][2] tagged granules of y
-    unsigned cgp_tag = 1;               // tag of the next launch's first iteration
     unsigned* cgp_sync = nullptr;
-    bool chain_oseg = false;  // the side chain of slot cgp_slot builds E from k_tl_cgp's segments (reissue_chain)
     // the coarse factorization of solve n runs on `side` while the CG of solve n uses slot (n-1)&1
     double *Ebuf[2]{}, *Einvbuf[2]{};
     double* gjW = nullptr;  // Gauss-Jordan ping-pong buffer [ldE][ldE]
@@ -142,14 +148,11 @@ struct insfm_ba {
     hipStream_t xstream = nullptr;
     // u_late: k_lin_cams runs on `aux` beside k_lin_points / k_schur; k_schur builds S / b without U / g_c and
     // k_cg_factor adds them after waiting for ev_lc (lin_join).  Single-rank W-path only.
-    bool u_late = false, lin_pending = false;
+    bool u_late = false;
     hipStream_t aux = nullptr;
     hipEvent_t ev_lin0 = nullptr, ev_lc = nullptr;
     hipEvent_t ev_x = nullptr, ev_xdone = nullptr;
     hipEvent_t ev_pre = nullptr;  // multi-rank: recorded in front of the CG (its stall deadline starts after it)
-    bool built_pending = false;
-    long long tl_solves = 0;
-    bool tl_fresh = false;  // no solve since the last linearization (the lag rule applies to that solve only)
     int coarse_used = 0;
     // global positioning (kind 1, insfm_gp_*): per local observation ray / scale-free flag / source index, camera
     // factors, the linearization records and the scale-eliminated camera blocks of the current trial
@@ -400,10 +403,10 @@ int with_model(int m, F&& f) {
         default: return INSFM_BA_EINVAL;
     }
 }
+// the camera-block sizes of the bundle adjustment's models; with_D: those and global positioning's 3
 template <typename F>
-int with_D(int D, F&& f) {
+int with_ba_D(int D, F&& f) {
     switch (D) {
-        case 3: return f(std::integral_constant<int, 3>{});  // global positioning
         case 7: return f(std::integral_constant<int, 7>{});
         case 8: return f(std::integral_constant<int, 8>{});
         case 9: return f(std::integral_constant<int, 9>{});
@@ -411,6 +414,11 @@ int with_D(int D, F&& f) {
         case 16: return f(std::integral_constant<int, 16>{});
         default: return INSFM_BA_EINVAL;
     }
+}
+template <typename F>
+int with_D(int D, F&& f) {
+    if (D == 3) return f(std::integral_constant<int, 3>{});
+    return with_ba_D(D, std::forward<F>(f));
 }
 
 int launch_err(insfm_ba* h, const char* what) {

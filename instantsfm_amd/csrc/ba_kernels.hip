@@ -16,8 +16,9 @@
 //                          ba_trial.h    k_backsub_rc (dp, trial points and cameras, gain terms), k_cost, k_final (the
 //                                        partials in a fixed order -> 64 B), k_publish (to the host's spin-wait)
 //   global positioning     ba_gp.h       the same solve with D = 3 and its own linearization
-//   host side              ba_handle.h, ba_solve.h, ba_step.h, lm_policy.h (the step), ba_create.h, create_plan.h
-//                          (creation), ba_debug_api.h (the debug ABI)
+//   host side              ba_handle.h; ba_solve.h executes what solve_policy.h plans (one solve), ba_step.h what
+//                          lm_policy.h and cg_poll.h decide (the step); ba_create.h, create_plan.h, create_host.h
+//                          (creation); ba_debug_api.h (the debug ABI)
 // With desc.deterministic = 1 every cross-workgroup reduction is a fixed-order partial sum (no float atomics in global
 // memory) and k_schur's workgroups run four waves that take their LDS adds in turn, so that each slot sees its
 // additions in a fixed order: a step is then bitwise reproducible.
@@ -184,7 +185,7 @@ int insfm_ba_set_ranks_per_device(insfm_ba* h, int32_t ranks) {
 
 int insfm_ba_cg_info(const insfm_ba* h, int32_t* out) {
     if (!h || !out) return INSFM_BA_EINVAL;
-    out[0] = h->xpart ? 3 : h->cgp_nb ? (h->cgp_det ? (h->adef2 ? 5 : 2) : (h->adef2 ? 4 : 1)) : 0;
+    out[0] = cg_path_code(h->xpart, h->cgp_nb, h->cgp_det, h->adef2);
     out[1] = h->cgp_grid;
     out[2] = h->cgp_slots;
     out[3] = h->cgp_nb;
@@ -213,9 +214,9 @@ int insfm_ba_reset(insfm_ba* h) {
     // survives) and the CG's first batch is sized as for a new handle
     cgp_drop_pending(h);
     if (int rc = side_flush(h)) return rc;
-    h->tl_solves = 0;
-    h->tl_fresh = false;
-    h->last_cg_iters = 16;
+    h->ss.tl_solves = 0;
+    h->ss.tl_fresh = false;
+    h->ss.last_cg_iters = 16;
     h->chain_timed[0] = h->chain_timed[1] = false;
     return INSFM_BA_OK;
 }

@@ -1,6 +1,6 @@
 // The LM step driver, host side: the trial cost and its published result, the repeats of a trial whose k_tl_cgp launch
-// did not converge, and lm_step.  The decisions live in lm_policy.h and cg_poll.h (CPU-tested); this file issues the
-// stream work.  Part of the one translation unit ba_kernels.hip (included after ba_solve.h, before ba_create.h).
+// did not converge, and lm_step.  The decisions live in lm_policy.h, solve_policy.h and cg_poll.h (CPU-tested); this
+// file issues the stream work.  Part of the translation unit ba_kernels.hip (after ba_solve.h, before ba_create.h).
 #pragma once
 #include "ba_solve.h"
 
@@ -9,62 +9,10 @@ namespace {
 // A step that ended in an error with a k_tl_cgp status unread: wait for the launch and restart the barrier counters
 // (the next launch's epochs would otherwise not match what this one counted).
 void cgp_drop_pending(insfm_ba* h) {
-    if (!h->cgp_pending) return;
-    h->cgp_pending = false;
+    if (!h->ss.cgp_pending) return;
+    h->ss.cgp_pending = false;
     (void)hipStreamSynchronize(h->stream);
     (void)cgp_reset_barriers(h);
-}
-
-// Multi-rank: every rank leaves k_tl_cgp after an abort on any rank (own status `st0`).  A rank whose k_tl_cgp
-// converged left its final CG vectors in place of r0, so r0 = L^-1 b is formed again from the completed S / b
-// (k_cg_factor without U / g_c: the same L, L^-1 and r0) before the basis / restriction and the launch-path CG.
-int cgp_collective_fallback(insfm_ba* h, int st0) {
-    std::fprintf(stderr, "[insfm] rank %d: a k_tl_cgp grid barrier timed out on %s rank; every rank continues on the "
-                         "launch-per-iteration CG\n", h->d.rank, st0 == 4 ? "this" : "another");
-    h->cgp_nb = 0;
-    h->cgp_lost = false;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    int rc;
-    if ((rc = cgp_reset_barriers(h))) return rc;
-    HIPCHK(hipMemsetAsync(h->cg.status, 0, sizeof(int) * 4, h->stream));
-    rc = with_D(h->D, [&](auto dc_) -> int {
-        launch_factor<decltype(dc_)::value>(h, 1.0, false, nullptr);  // (the factorization alone)
-        return launch_err(h, "k_cg_factor");
-    });
-    if (rc || (rc = ensure_sn(h)) || (rc = run_tl_basis(h, h->cams_cur, h->stream))) return rc;
-    return reissue_chain(h);
-}
-
-// The persistent CG's factorization and coarse basis again on the completed S / b (no U / g_c added: the same L,
-// L^-1 and r0 = L^-1 b): k_cg_factor_basis, or (a handle whose solves did not form the basis there) k_cg_factor and
-// k_tl_basis.
-int refactor_for_cgp(insfm_ba* h, const double* cams) {
-    const int rc = with_D(h->D, [&](auto dc_) -> int {
-        launch_factor<decltype(dc_)::value>(h, 1.0, false, cams);
-        return launch_err(h, h->basis_by_factor ? "k_cg_factor_basis" : "k_cg_factor");
-    });
-    if (rc) return rc;
-    return h->basis_by_factor ? 0 : run_tl_basis(h, cams, h->stream);
-}
-
-// An A-DEF2 solve that broke down (k_tl_cgp status 2).  Its soundness rests on the coarse start x0 making
-// Z~^T r exactly zero, which holds only with the solve's own coarse inverse; under the lag rule E^-1 is the previous
-// solve's, the preconditioner is not symmetric on the iterates, and the single-reduction recurrence can break down.
-// The trial's solve is then repeated with the additive coarse correction (precond 1, symmetric for any SPD E^-1) on
-// the same handle: r0 = L^-1 b, the basis and the restriction of r0 again from the completed S / b
-// (refactor_for_cgp), one additive k_tl_cgp launch.  Every rank of a replicated
-// multi-rank CG sees the same status (bitwise-equal fixed-order arithmetic), so every rank repeats it.
-int adef2_fallback(insfm_ba* h, int it_failed, int* st) {
-    std::fprintf(stderr, "[insfm] A-DEF2 PCG breakdown at iteration %d: the trial's solve is repeated with the additive "
-                         "coarse correction\n", it_failed);
-    ++h->adef2_fallbacks;
-    HIPCHK(hipMemsetAsync(h->cg.status, 0, sizeof(int) * 4, h->stream));
-    int rc = refactor_for_cgp(h, h->cams_cur);
-    if (rc) return rc;
-    h->adef2 = false;
-    rc = run_tl_cg(h, st);
-    h->adef2 = true;
-    return rc;
 }
 
 // lm_step's accept rule for the trial being costed (k_publish copies an accepted trial into the caller's buffers)
@@ -87,7 +35,7 @@ int finish_cost(insfm_ba* h, const TrialAccept* ta) {
     const bool copy = ta != nullptr && h->ext_cur && h->kind == 0;
     const long long ncam = copy ? (long long)h->C * h->stride : 0, npts = copy ? (long long)h->Pl * 3 : 0;
     const int grid = copy ? std::max(1, std::min(1024, cdiv(std::max(ncam, npts / 2 + 1), kThreads))) : 1;
-    k_publish<<<grid, kThreads, 0, h->stream>>>(h->result, h->cgp_pending ? h->cg.status : nullptr, h->pub_dev, seq,
+    k_publish<<<grid, kThreads, 0, h->stream>>>(h->result, h->ss.cgp_pending ? h->cg.status : nullptr, h->pub_dev, seq,
                                                ta ? ta->last : 0.0, ta ? ta->can_reject : 0,
                                                h->cams_new, copy ? h->cams_cur : nullptr, ncam, h->pts_new, h->pts_cur, npts,
                                                stamp_ptr(h, kStPublish));
@@ -121,20 +69,15 @@ int finish_cost(insfm_ba* h, const TrialAccept* ta) {
 // cost at (cams, pts_local) -> h->result[0..1]; with gain partials when `gains` (after a solve).
 int run_cost(insfm_ba* h, const double* cams, const double* pts_local, bool gains, const double* scl = nullptr,
              const TrialAccept* ta = nullptr) {
-    if (h->kind == 1) {
+    const bool gpk = h->kind == 1;  // (global positioning publishes without an accept rule)
+    if (gpk) {
         if (h->Nl > 0)
             k_gp_cost<<<h->n_cost, kThreads, 0, h->stream>>>(h->Nl, h->cam, h->ptl, h->trans, h->fcam, cams, pts_local, scl,
                                                              h->d.huber_delta, h->part_cost);
         k_final<<<1, kFinalThreads, 0, h->stream>>>(h->part_cost, h->Nl > 0 ? h->n_cost : 0, gains && h->Pl > 0 ? h->part_gp : nullptr,
                                                h->n_gp, nullptr, 0, h->flags, h->result, nullptr);
-        int rc = launch_err(h, "k_gp_cost/k_final");
-        if (rc) return rc;
-        h->flags_dirty = false;
-        rc = allreduce(h, h->result, 6);
-        if (rc) return rc;
-        return finish_cost(h, nullptr);
     }
-    int rc = with_model(h->model, [&](auto mc) -> int {
+    int rc = gpk ? launch_err(h, "k_gp_cost/k_final") : with_model(h->model, [&](auto mc) -> int {
         constexpr int M = decltype(mc)::value;
         if (h->Nl > 0)
             k_cost<M><<<h->n_cost, kCostThreads, 0, h->stream>>>(h->Nl, h->cam, h->ptl, h->uv, h->pp, cams, pts_local,
@@ -142,35 +85,42 @@ int run_cost(insfm_ba* h, const double* cams, const double* pts_local, bool gain
                                                              gains ? stamp_ptr(h, kStCost) : nullptr);
         k_final<<<1, kFinalThreads, 0, h->stream>>>(h->part_cost, h->Nl > 0 ? h->n_cost : 0, gains && h->Pl > 0 ? h->part_gp : nullptr,
                                                h->n_gp, gains ? h->part_gc : nullptr, h->n_gc, h->flags, h->result,
-                                               h->cgp_pending ? h->cg.status : nullptr,
+                                               h->ss.cgp_pending ? h->cg.status : nullptr,
                                                gains ? stamp_ptr(h, kStFinal) : nullptr);
         return launch_err(h, "k_cost/k_final");
     });
     if (rc) return rc;
-    h->flags_dirty = false;
+    h->ss.flags_dirty = false;
     rc = allreduce(h, h->result, 6);
     if (rc) return rc;
-    return finish_cost(h, ta);
+    return finish_cost(h, gpk ? nullptr : ta);
 }
 
 // A trial whose k_tl_cgp launch (status cst, read behind the trial's cost) did not converge, once more: the CG again
-// after the preparation `how` names, then cg_tail, the back-substitution and the cost (k_publish accepted the first
-// nowhere: its CG did not converge).  Returns the PCG iterations, INSFM_BA_ESOLVER (from cg_tail alone) or an error.
+// by the recipe of `how` (solve_policy.h repeat_recipe, ba_solve.h repeat_cg), then cg_tail, the back-substitution and
+// the cost (k_publish accepted the first nowhere: its CG did not converge).  Returns the PCG iterations,
+// INSFM_BA_ESOLVER (from cg_tail alone) or an error.
 int repeat_trial(insfm_ba* h, double f, const TrialAccept& ta, CgpNext how, const int* cst) {
-    int* st = reinterpret_cast<int*>(h->host_res + 8);
-    int rc;
     if (how == kRepeatCollective) {
         // a replicated multi-rank CG: some rank's k_tl_cgp timed out at a grid barrier (the all-reduced flag, the same
         // on every rank).  Every rank leaves the persistent CG for good and repeats the solve on the launch path from
         // r0 -- the same fixed-order arithmetic everywhere, so the ranks' dc stay bitwise equal.
-        if ((rc = cgp_collective_fallback(h, cst[0])) || (rc = run_tl_cg(h, st))) return rc;
-    } else if (how == kRepeatLaunchPath) {
-        // single rank: a grid barrier timed out (cgp_complete switched the handle to the launch path)
-        if ((rc = relaunch_on_launch_path(h, h->cams_cur, st))) return rc;
-    } else {  // kRepeatAdditive: an A-DEF2 breakdown
-        if ((rc = adef2_fallback(h, cst[1], st))) return rc;
-    }
-    const int it = cg_tail(h, st);
+        std::fprintf(stderr, "[insfm] rank %d: a k_tl_cgp grid barrier timed out on %s rank; every rank continues on the "
+                             "launch-per-iteration CG\n", h->d.rank, cst[0] == 4 ? "this" : "another");
+    } else if (how == kRepeatAdditive) {
+        // An A-DEF2 solve that broke down (k_tl_cgp status 2): under the lag rule E^-1 is the previous solve's, Z~^T r
+        // is not exactly zero and the single-reduction recurrence can break down.  The solve is
+        // repeated with the additive coarse correction (precond 1, symmetric for any SPD E^-1) in one k_tl_cgp launch.
+        // Every rank of a replicated multi-rank CG sees the same status (fixed-order arithmetic), so every rank does.
+        std::fprintf(stderr, "[insfm] A-DEF2 PCG breakdown at iteration %d: the trial's solve is repeated with the additive "
+                             "coarse correction\n", cst[1]);
+        ++h->adef2_fallbacks;
+    }  // (kRepeatLaunchPath, a single rank's time-out: cgp_complete reported it and left the persistent CG)
+    const RepeatRecipe recipe = repeat_recipe(how, h->last.basis_by_factor);
+    int* st = reinterpret_cast<int*>(h->host_res + 8);
+    int rc;
+    if ((rc = repeat_cg(h, recipe, st))) return rc;
+    const int it = cg_tail(h, recipe.additive, st);
     if (it < 0) return it;
     if ((rc = solve_tail(h, f, h->cams_cur, h->pts_cur, h->dc))) return rc;
     if ((rc = run_cost(h, h->cams_new, h->pts_new, true, h->scl_new, &ta))) return rc;
@@ -242,26 +192,24 @@ int lm_step(insfm_ba* h, insfm_ba_stats* st) {
     for (;;) {
         f *= (1.0 + h->damping);
         ++trials;
-        h->cg_async = true;  // (a k_tl_cgp solve: its status is read after the trial's cost, below)
-        int it = run_solve(h, f, h->cams_cur, h->pts_cur);
-        h->cg_async = false;
+        int it = run_solve(h, f, h->cams_cur, h->pts_cur, true);  // (a k_tl_cgp status is read after the cost, below)
         if (it == INSFM_BA_ESOLVER) { failed = 1; h->loss = last; break; }
         if (it < 0) return it;
         rec(h, kEvCost);
         const TrialAccept ta{last, rejects < h->d.max_rejects ? 1 : 0};
         if ((rc = run_cost(h, h->cams_new, h->pts_new, true, h->scl_new, &ta))) return rc;  // waits for the result
-        if (h->cgp_pending) {  // the k_tl_cgp launch finished before the k_publish the host just saw
-            h->cgp_pending = false;
+        if (h->ss.cgp_pending) {  // the k_tl_cgp launch finished before the k_publish the host just saw
+            h->ss.cgp_pending = false;
             int cst[3];
-            if ((rc = cgp_complete(h, cst))) return rc;
+            if ((rc = cgp_complete(h, h->adef2, cst))) return rc;
             if (h->timing) acc_time(h, kEvCg, kEvCgEnd, kPhCgLaunches);
             const bool not_spd = h->host_res[4] != 0.0;  // a damped point block was not SPD
             const CgpNext next = cgp_next(cst[0], not_spd, h->d.world_size > 1 || h->d.allreduce, h->host_res[5] != 0.0,
-                                          h->cgp_lost, h->adef2);
+                                          h->ss.cgp_lost, h->adef2);
             if (next == kConverged) {
                 it = cst[1];
                 h->coarse_used = cst[2];
-                h->last_cg_iters = it;
+                h->ss.last_cg_iters = it;
             } else if (next == kFailStep || next == kDeviceError) {
                 if (!not_spd) h->err = pcg_status_message(cst[0], cst[1], kCgpLaunch);
                 if (next == kDeviceError) return INSFM_BA_EHIP;

@@ -1,4 +1,4 @@
-// Host poll policy of the two-level CG (ba_solve.h run_tl_cg): no stream sync inside the CG.  The lead workgroup
+// Host poll policy of the two-level CG (ba_solve.h cg_wait): no stream sync inside the CG.  The lead workgroup
 // of k_tl_pc publishes {iterations started, status} into host-mapped memory; the host keeps about `ahead` iterations
 // queued, one at a time, and stops when the status word turns non-zero.  Plain C++ (no HIP types) so the policy,
 // including its deadline, is unit-tested on the CPU (tests/test_cg_poll.py builds tests/cpp/cg_poll_test.cpp).

@@ -1174,7 +1174,7 @@ int ora_pcg(ora_t* h, double* xout) {
     }
     /* A-DEF2 breakdown (the recurrence's denominator <= 0: possible under the lag rule, whose E^-1 is the previous
      * solve's, so Z~^T r is not exactly zeroed by the coarse start): the solve is repeated from r0 with the additive
-     * correction (pass 1), as the GPU's adef2_fallback does. */
+     * correction (pass 1), as the GPU's repeat_trial (kRepeatAdditive) does. */
     for (int pass = 0;; ++pass) {
     for (int i = 0; i < C; ++i) {
         const double* Li = h->Minv + (size_t)i * DD;

@@ -1,4 +1,4 @@
-"""CPU unit test of the two-level CG host poll policy (instantsfm_amd/csrc/cg_poll.h, used by ba_solve.h run_tl_cg):
+"""CPU unit test of the two-level CG host poll policy (instantsfm_amd/csrc/cg_poll.h, used by ba_solve.h cg_wait):
 progress, convergence, the launch limit, stream errors, and the wall-clock stall deadline that turns a CG launch that
 never publishes into INSFM_BA_EHIP instead of an endless spin; and the bounded wait for a trial cost (publish_wait,
 used by ba_step.h finish_cost)."""
