@@ -42,6 +42,11 @@ int insfm_tracks_establish(int64_t n_nodes, const int32_t* node_img, const void*
                            int32_t* track_root, uint8_t* track_bad, int32_t* track_nodes, int32_t* row_node,
                            int32_t* row_track, int64_t* counts, void* stream);
 
+/* Co-visibility pair counts over the finished tracks (pruning): documented in insfm_covis.h, which declares it too. */
+int insfm_covis_pairs(int64_t n_tracks, const int64_t* track_ptr, const int32_t* obs_img, int32_t min_count,
+                      int64_t capacity, int32_t* pair_lo, int32_t* pair_hi, int32_t* pair_count,
+                      int64_t* pair_first, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,7 +56,7 @@ class Stats(ctypes.Structure):
 
 
 # exported symbols (every one declared in include/*.h): the product ABI (insfm_ba.h, insfm_gp.h, insfm_passes.h,
-# insfm_tracks.h) and the introspection / prototype entry points of insfm_ba_debug.h
+# insfm_tracks.h, insfm_covis.h) and the introspection / prototype entry points of insfm_ba_debug.h
 PUBLIC_SYMBOLS = ("insfm_build_info", "insfm_ba_default_desc", "insfm_ba_create", "insfm_ba_step", "insfm_ba_cost",
                   "insfm_ba_reset", "insfm_ba_destroy", "insfm_ba_last_error", "insfm_ba_exchange_count",
                   "insfm_ba_set_exchange", "insfm_ba_set_timing", "insfm_ba_release_cache",
@@ -65,7 +65,7 @@ PUBLIC_SYMBOLS = ("insfm_build_info", "insfm_ba_default_desc", "insfm_ba_create"
                   "insfm_gp_default_desc", "insfm_gp_create", "insfm_gp_step", "insfm_gp_cost",
                   "insfm_undistort", "insfm_filter_reproj_normalized", "insfm_filter_angle", "insfm_filter_tri_angle",
                   "insfm_filter_reproj_pixel", "insfm_reproj_candidates",
-                  "insfm_tracks_establish")
+                  "insfm_tracks_establish", "insfm_covis_pairs")
 DEBUG_SYMBOLS = ("insfm_ba_debug_linearize", "insfm_ba_debug_solve", "insfm_ba_debug_get", "insfm_ba_nnzb",
                  "insfm_ba_debug_time_kernel", "insfm_ba_debug_clusters", "insfm_ba_debug_spd_inverse",
                  "insfm_ba_debug_time_cgp", "insfm_ba_debug_stamps",
@@ -195,6 +195,8 @@ def load(path=None):
     L.insfm_reproj_candidates.argtypes = [i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, f64, vp, vp, vp]
     L.insfm_tracks_establish.argtypes = [i64, vp, vp, i32, i64, vp, vp, f64, vp, vp, vp, vp, vp,
                                          ctypes.POINTER(ctypes.c_int64), vp]
+    L.insfm_covis_pairs.argtypes = [i64, vp, vp, i32, i64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
+    L.insfm_covis_pairs.restype = ctypes.c_int
     for fn in ("insfm_tracks_establish", "insfm_undistort", "insfm_filter_reproj_normalized", "insfm_filter_angle", "insfm_filter_tri_angle",
                "insfm_filter_reproj_pixel", "insfm_reproj_candidates",
            "insfm_tracks_establish"):

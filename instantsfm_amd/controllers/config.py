@@ -2,8 +2,9 @@
 
 Same ``GENERAL_OPTIONS`` keys and defaults and the same ``Config(feature_name, manual_config_name=None)`` attributes.
 The stages this build does not replace (preprocessing, view-graph calibration, relative pose estimation, rotation
-averaging, pruning: SURVEY.md section 7) keep their ``skip_*`` switches; ``SolveGlobalMapper`` requires them to be set
-(``Config.for_ba_half`` sets them) and raises NotImplementedError otherwise.
+averaging: SURVEY.md section 7) keep their ``skip_*`` switches; ``SolveGlobalMapper`` requires them to be set
+(``Config.for_ba_half`` sets them) and raises NotImplementedError otherwise.  Pruning runs when ``skip_pruning`` is
+off (``for_ba_half(pruning=True)``); it is skipped by default, as in the reference.
 """
 import copy
 import importlib
@@ -24,9 +25,9 @@ GENERAL_OPTIONS = {
     'uniform_camera': True,
 }
 
-# the stages before track establishment and after retriangulation (global_mapper.py:22-78, :148-154)
+# the stages before track establishment (global_mapper.py:22-78)
 OUT_OF_SCOPE_STAGES = ('skip_preprocessing', 'skip_view_graph_calibration', 'skip_relative_pose_estimation',
-                       'skip_rotation_averaging', 'skip_pruning')
+                       'skip_rotation_averaging')
 
 
 class Config:
@@ -55,12 +56,14 @@ class Config:
         self.FEATURE_HANDLER_OPTIONS = copy.deepcopy(CONFIG['FEATURE_HANDLER_OPTIONS'])
 
     @classmethod
-    def for_ba_half(cls, feature_name='colmap', retriangulation=True, manual_config_name=None):
+    def for_ba_half(cls, feature_name='colmap', retriangulation=True, manual_config_name=None, pruning=False):
         """The configuration the mapper runs with here: the out-of-scope stages skipped (their outputs -- pair
         inliers, registered images with rotations -- are supplied by the caller), track establishment, global
-        positioning and bundle adjustment on, retriangulation on unless ``retriangulation`` is False."""
+        positioning and bundle adjustment on, retriangulation on unless ``retriangulation`` is False, pruning off (the
+        reference default) unless ``pruning`` is True."""
         cfg = cls(feature_name, manual_config_name)
         for k in OUT_OF_SCOPE_STAGES:
             cfg.OPTIONS[k] = True
         cfg.OPTIONS['skip_retriangulation'] = not retriangulation
+        cfg.OPTIONS['skip_pruning'] = not pruning
         return cfg

@@ -1,9 +1,10 @@
 """SolveGlobalMapper -- drop-in for ``instantsfm/controllers/global_mapper.py`` (reference :21-156), the half of it
-this build replaces: track establishment (:80-91), global positioning (:93-107), the bundle-adjustment block (:109-126)
-and retriangulation (:128-146), every stage on the MI355X processors of this package.
+this build replaces: track establishment (:80-91), global positioning (:93-107), the bundle-adjustment block (:109-126),
+retriangulation (:128-146) and pruning (:148-154, off by default like the reference's), every stage on the MI355X
+processors of this package.
 
 The stages before track establishment (preprocessing, view-graph calibration, relative pose estimation, rotation
-averaging: :22-78) and pruning (:148-154) are outside the hot-path scope.  Their ``skip_*``
+averaging: :22-78) are outside the hot-path scope.  Their ``skip_*``
 switches must be set; their outputs -- each valid pair's ``inliers`` and each image's ``is_registered`` flag and
 world-to-camera rotation -- are the caller's (``synth.stand_in_rotation_averaging`` supplies them for synthetic
 databases).  With a switch left off the mapper raises NotImplementedError instead of silently skipping the stage.
@@ -11,7 +12,9 @@ databases).  With a switch left off the mapper raises NotImplementedError instea
 ``timings`` (optional dict) receives the wall time of every stage and, per TorchGP / TorchBA call, its
 pack / create / steps / write-back split (``TorchGP.timings`` / ``TorchBA.timings``); ``timings['trace']`` lists
 (stage, tracks, observations, final LM loss or RMSE) after every stage -- what the tests' CPU restatement of the
-pipeline records too, so the two can be compared stage by stage.
+pipeline records too, so the two can be compared stage by stage.  Pruning adds ``timings['pruning_s']`` and a last
+trace entry ``('pruned', tracks, observations, None)``; it changes ``image.is_registered`` and ``image.cluster_id``, not
+the tracks.
 """
 import time
 
@@ -19,6 +22,7 @@ from ..processors.bundle_adjustment import TorchBA
 from ..processors.global_positioning import TorchGP
 from ..processors.image_undistortion import UndistortImages
 from ..processors.reconstruction_normalizer import NormalizeReconstruction
+from ..processors.reconstruction_pruning import PruneWeaklyConnectedImages
 from ..processors.track_establishment import TrackEngine
 from ..processors.track_filter import (FilterTracksByAngle, FilterTracksByReprojectionNormalized,
                                        FilterTracksTriangulationAngle, collect_tracks)
@@ -44,7 +48,7 @@ def SolveGlobalMapper(view_graph, cameras, images, config, depths=None, visualiz
     """global_mapper.py:21-156 from track establishment on.  Returns (cameras, images, tracks) like the reference."""
     for key in OUT_OF_SCOPE_STAGES:
         if not config.OPTIONS[key]:
-            raise NotImplementedError(f"{key}=False: that stage (global_mapper.py:22-78 / :148-154) is outside this "
+            raise NotImplementedError(f"{key}=False: that stage (global_mapper.py:22-78) is outside this "
                                       "build's scope; set the switch and supply its outputs (pair inliers, "
                                       "registered images with rotations)")
     T = timings if timings is not None else {}
@@ -128,5 +132,13 @@ def SolveGlobalMapper(view_graph, cameras, images, config, depths=None, visualiz
         trace.append(('retri_filtered', len(tracks), _n_obs(tracks), None))
         T['retriangulation_s'] = time.time() - start_time
         print('Retriangulation took: ', T['retriangulation_s'])
+
+    if not config.OPTIONS['skip_pruning']:                                                      # :148-154
+        _banner('Running postprocessing ...')
+        start_time = time.time()
+        PruneWeaklyConnectedImages(images, tracks, device=device)
+        trace.append(('pruned', len(tracks), _n_obs(tracks), None))
+        T['pruning_s'] = time.time() - start_time
+        print('Postprocessing took: ', T['pruning_s'])
 
     return cameras, images, tracks

@@ -7,12 +7,13 @@ Restates the subset of ``instantsfm/scene/defs.py`` that ``TorchBA.Solve`` reads
 * ``get_camera_model_info`` -- defs.py:115-140 (focal / pp / k index maps)
 * ``Camera``              -- defs.py:142-237 (``model_id``, ``params``, ``set_params``)
 * ``Track``               -- defs.py:414-423 (``xyz``, ``observations`` [k,2] = (image_id, feature_id))
-* ``ConfigurationType``, ``ImagePair``, pair-id helpers, ``ViewGraph`` (pairs only) -- defs.py:41-97, 425-430: what
-  the COLMAP database reader produces and the track engine consumes
+* ``ConfigurationType``, ``ImagePair``, pair-id helpers, ``ViewGraph`` -- defs.py:41-97, 425-509: what the COLMAP database
+  reader produces and the track engine consumes, and the connected components pruning works on
 
 The reference module imports cv2 for undistortion helpers that are off the BA path; this
 restatement has no cv2 dependency.
 """
+from collections import deque
 from enum import Enum
 from typing import List, Optional
 
@@ -93,7 +94,8 @@ def Ids2PairId(id1, id2):
 
 
 class ViewGraph:
-    """defs.py:425-430 plus establish_adjacency_list (:431-441)."""
+    """defs.py:425-509: the pairs, establish_adjacency_list (:431-441) and the connected-component helpers pruning
+    uses (:443-509)."""
 
     def __init__(self):
         self.image_pairs = {}  # pair_id -> ImagePair
@@ -107,6 +109,57 @@ class ViewGraph:
                 continue
             self.adjacency_list.setdefault(pair.image_id1, set()).add(pair.image_id2)
             self.adjacency_list.setdefault(pair.image_id2, set()).add(pair.image_id1)
+
+    def BFS(self, root):
+        """defs.py:443-457: the images reachable from ``root`` over the adjacency list, marked in ``self.visited``."""
+        self.visited[root] = True
+        component = [root]
+        queue = deque(component)
+        while queue:
+            for neighbor in self.adjacency_list[queue.popleft()]:
+                if not self.visited[neighbor]:
+                    self.visited[neighbor] = True
+                    component.append(neighbor)
+                    queue.append(neighbor)
+        return component
+
+    def find_connected_component(self):
+        """defs.py:459-468: components in the order their first image appears among the adjacency keys (pair by pair,
+        ``image_id1`` before ``image_id2``)."""
+        self.visited = dict.fromkeys(self.adjacency_list, False)
+        self.connected_component = [self.BFS(image_id) for image_id in self.adjacency_list if not self.visited[image_id]]
+
+    def keep_largest_connected_component(self, images):
+        """defs.py:470-491: only the largest component stays registered (of equally large ones the first found); pairs
+        touching an unregistered image become invalid.  False when there is no component at all."""
+        self.establish_adjacency_list()
+        self.find_connected_component()
+        largest = None
+        for component in self.connected_component:
+            if len(component) > (len(largest) if largest is not None else 0):
+                largest = component
+        if largest is None:
+            return False
+        members = set(largest)
+        for image in images:
+            image.is_registered = image.id in members
+        for pair in self.image_pairs.values():
+            if not (images[pair.image_id1].is_registered and images[pair.image_id2].is_registered):
+                pair.is_valid = False
+        return True
+
+    def mark_connected_components(self, images):
+        """defs.py:493-509: ``image.cluster_id`` = rank of the image's component by size (descending, stable), -1 for
+        images in none.  Returns the number of components (1 when there is none, as the reference does)."""
+        self.establish_adjacency_list()
+        self.find_connected_component()
+        by_size = sorted(self.connected_component, key=len, reverse=True)  # (stable: ties keep discovery order)
+        for image in images:
+            image.cluster_id = -1
+        for cluster, component in enumerate(by_size):
+            for image_id in component:
+                images[image_id].cluster_id = cluster
+        return max(len(by_size), 1)
 
 
 class CameraModelId(Enum):

@@ -17,6 +17,8 @@ records:
   ``points_2d``, ``camera_indices``, ``point_indices``, ``camera_pps`` and the model's ``pose`` /
   ``points_3d`` parameters, together with the scene that produced them.  The LM shim raises after
   capturing its input, so nothing past bundle_adjustment.py:132 runs.
+* ``pruning_golden.npz`` (``--only pruning``) -- ``PruneWeaklyConnectedImages`` (reconstruction_pruning.py:172-210) on
+  the scenes of tests/pruning_scene.py: the visibility graph in dict order, the threshold, the resulting flags.
 
 Only data leaves this script: no reference source is copied into the repository.
 Usage:  python tools/gen_golden.py [--out tests/golden]
@@ -718,10 +720,83 @@ def gen_depth(out_dir):
     print("depth_sample.npz", len(res["feats"]), "features; border raises", raised)
 
 
+def _ref_prune(RP, ref_defs, PS, sc, reorder=False):
+    """The reference's PruneWeaklyConnectedImages on one scene, its module-level EstablishStrongClusters wrapped so
+    that the call's arguments are recorded before it runs.  ``reorder`` re-keys the visibility graph in pair-id order
+    before clustering (to find the scenes whose outcome depends on the dict order).  Returns None on an empty graph."""
+    import contextlib
+    import io
+    images, tracks = PS.as_objects(*sc, image_cls=ref_defs.Image, track_cls=ref_defs.Track)
+    rec = {}
+    inner = RP.EstablishStrongClusters
+
+    def recording(view_graph, imgs, threshold, min_num_images):
+        if reorder:
+            view_graph.image_pairs = dict(sorted(view_graph.image_pairs.items()))
+        rec["pairs"] = np.array([[p.image_id1, p.image_id2, p.weight] for p in view_graph.image_pairs.values()],
+                                dtype=np.int64).reshape(-1, 3)
+        rec["threshold"] = np.array(threshold)
+        return inner(view_graph, imgs, threshold, min_num_images)
+    RP.EstablishStrongClusters = recording
+    try:
+        with contextlib.redirect_stdout(io.StringIO()):
+            RP.PruneWeaklyConnectedImages(images, tracks)
+    except IndexError:
+        return None
+    finally:
+        RP.EstablishStrongClusters = inner
+    rec["registered"] = np.array([im.is_registered for im in images])
+    rec["cluster"] = np.array([im.cluster_id for im in images], dtype=np.int64)
+    return rec
+
+
+def gen_pruning(out_dir):
+    """PruneWeaklyConnectedImages (reconstruction_pruning.py:172-210) on the scenes of tests/pruning_scene.py: the
+    inputs, the visibility graph in dict order as EstablishStrongClusters receives it, the threshold, and the
+    resulting registration flags and cluster ids.  Also reports, over seeds 0-299, which scenes unregister an image,
+    give several clusters, or change when the pairs are taken in key order -- the committed seeds (pruning_scene.SEEDS)
+    were picked from that list."""
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import pruning_scene as PS
+    from instantsfm.processors import reconstruction_pruning as RP
+    from instantsfm.scene import defs as ref_defs
+    kinds = {"unregisters": [], "clusters": [], "order": [], "empty": []}
+    for seed in range(300):
+        sc = PS.random_scene(seed)
+        rec = _ref_prune(RP, ref_defs, PS, sc)
+        if rec is None:
+            kinds["empty"].append(seed)
+            continue
+        alt = _ref_prune(RP, ref_defs, PS, sc, reorder=True)
+        if not rec["registered"].all():
+            kinds["unregisters"].append(seed)
+        if rec["cluster"].max() > 0:
+            kinds["clusters"].append(seed)
+        if not (np.array_equal(rec["registered"], alt["registered"]) and np.array_equal(rec["cluster"], alt["cluster"])):
+            kinds["order"].append(seed)
+    for k, v in kinds.items():
+        print(f"seeds 0-299 {k}: {len(v)}: {v}")
+    res = {}
+    for name in PS.names():
+        M, ptr, img = PS.scene(name)
+        rec = _ref_prune(RP, ref_defs, PS, (M, ptr, img))
+        res[f"{name}_M"] = np.array(M)
+        res[f"{name}_track_ptr"] = ptr.astype(np.uint16 if ptr[-1] < 2 ** 16 else np.int64)
+        res[f"{name}_obs_img"] = img.astype(np.uint8 if M <= 256 else np.int32)
+        for k, v in rec.items():
+            res[f"{name}_{k}"] = v
+    path = os.path.join(out_dir, "pruning_golden.npz")
+    np.savez_compressed(path, **res)
+    print("pruning_golden.npz", len(PS.names()), "scenes,", os.path.getsize(path), "bytes;",
+          "committed seeds per kind:", {k: len(set(v) & set(PS.SEEDS)) for k, v in kinds.items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", choices=("projection", "packing", "gp", "passes", "retri", "tracks", "depth"), default=None)
+    ap.add_argument("--only", choices=("projection", "packing", "gp", "passes", "retri", "tracks", "depth", "pruning"),
+                    default=None)
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     with tempfile.TemporaryDirectory():
@@ -742,6 +817,8 @@ def main():
             gen_tracks(args.out)
         if args.only in (None, "depth"):
             gen_depth(args.out)
+        if args.only in (None, "pruning"):
+            gen_pruning(args.out)
 
 
 if __name__ == "__main__":
