@@ -47,6 +47,13 @@ int insfm_covis_pairs(int64_t n_tracks, const int64_t* track_ptr, const int32_t*
                       int64_t capacity, int32_t* pair_lo, int32_t* pair_hi, int32_t* pair_count,
                       int64_t* pair_first, int64_t* counts, void* stream);
 
+/* Image-pair inlier scoring over the matches (before the tracks exist): documented in insfm_pairs.h, which declares it
+ * too. */
+int insfm_pair_inliers(int64_t n_pairs, const int64_t* pair_ptr, int64_t n_matches, const int32_t* match_a,
+                       const int32_t* match_b, int64_t n_features, const void* xy, int32_t xy_f32, const void* rays,
+                       int32_t rays_f32, const int32_t* pair_kind, const double* pair_geom, int32_t* inlier_idx,
+                       int32_t* inlier_count, double* score, int32_t* touched, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,7 +65,7 @@ PUBLIC_SYMBOLS = ("insfm_build_info", "insfm_ba_default_desc", "insfm_ba_create"
                   "insfm_gp_default_desc", "insfm_gp_create", "insfm_gp_step", "insfm_gp_cost",
                   "insfm_undistort", "insfm_filter_reproj_normalized", "insfm_filter_angle", "insfm_filter_tri_angle",
                   "insfm_filter_reproj_pixel", "insfm_reproj_candidates",
-                  "insfm_tracks_establish", "insfm_covis_pairs")
+                  "insfm_tracks_establish", "insfm_covis_pairs", "insfm_pair_inliers")
 DEBUG_SYMBOLS = ("insfm_ba_debug_linearize", "insfm_ba_debug_solve", "insfm_ba_debug_get", "insfm_ba_nnzb",
                  "insfm_ba_debug_time_kernel", "insfm_ba_debug_clusters", "insfm_ba_debug_spd_inverse",
                  "insfm_ba_debug_time_cgp", "insfm_ba_debug_stamps",
@@ -197,6 +197,8 @@ def load(path=None):
                                          ctypes.POINTER(ctypes.c_int64), vp]
     L.insfm_covis_pairs.argtypes = [i64, vp, vp, i32, i64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
     L.insfm_covis_pairs.restype = ctypes.c_int
+    L.insfm_pair_inliers.argtypes = [i64, vp, i64, vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.insfm_pair_inliers.restype = ctypes.c_int
     for fn in ("insfm_tracks_establish", "insfm_undistort", "insfm_filter_reproj_normalized", "insfm_filter_angle", "insfm_filter_tri_angle",
                "insfm_filter_reproj_pixel", "insfm_reproj_candidates",
            "insfm_tracks_establish"):

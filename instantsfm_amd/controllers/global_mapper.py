@@ -15,14 +15,23 @@ pack / create / steps / write-back split (``TorchGP.timings`` / ``TorchBA.timing
 pipeline records too, so the two can be compared stage by stage.  Pruning adds ``timings['pruning_s']`` and a last
 trace entry ``('pruned', tracks, observations, None)``; it changes ``image.is_registered`` and ``image.cluster_id``, not
 the tracks.
+
+``pair_inliers=True`` makes the mapper produce the pairs' ``inliers`` itself, as reference lines :46-56 do after
+relative pose estimation: UndistortImages, ImagePairInliersCount (every match against the pair's H, F, or E plus relative
+pose, on the GPU), FilterInlierNum, FilterInlierRatio and ``view_graph.keep_largest_connected_component``.  The caller
+supplies each pair's relative pose (``rotation`` xyzw, ``translation``), plus ``F`` / ``H`` where the pair's config
+needs them.  It adds ``timings['pair_inliers_s']`` and a first trace entry ``('pair_inliers', valid pairs, total
+inliers, None)``.  Relative pose estimation itself stays out of scope, and so does its ``skip_*`` switch.
 """
 import time
 
 from ..processors.bundle_adjustment import TorchBA
 from ..processors.global_positioning import TorchGP
+from ..processors.image_pair_inliers import ImagePairInliersCount
 from ..processors.image_undistortion import UndistortImages
 from ..processors.reconstruction_normalizer import NormalizeReconstruction
 from ..processors.reconstruction_pruning import PruneWeaklyConnectedImages
+from ..processors.relpose_filter import FilterInlierNum, FilterInlierRatio
 from ..processors.track_establishment import TrackEngine
 from ..processors.track_filter import (FilterTracksByAngle, FilterTracksByReprojectionNormalized,
                                        FilterTracksTriangulationAngle, collect_tracks)
@@ -44,8 +53,10 @@ def _banner(msg):
 
 
 def SolveGlobalMapper(view_graph, cameras, images, config, depths=None, visualizer=None, device="cuda:0",
-                      timings=None, progress=False):
-    """global_mapper.py:21-156 from track establishment on.  Returns (cameras, images, tracks) like the reference."""
+                      timings=None, progress=False, pair_inliers=False):
+    """global_mapper.py:21-156 from track establishment on.  Returns (cameras, images, tracks) like the reference.
+    ``pair_inliers=True`` first scores every valid pair's matches and thins the view graph (:46-56 without
+    EstimateRelativePose)."""
     for key in OUT_OF_SCOPE_STAGES:
         if not config.OPTIONS[key]:
             raise NotImplementedError(f"{key}=False: that stage (global_mapper.py:22-78) is outside this "
@@ -55,6 +66,20 @@ def SolveGlobalMapper(view_graph, cameras, images, config, depths=None, visualiz
     T.setdefault('ba', [])
     trace = T.setdefault('trace', [])
     tracks = tracks_orig = None
+
+    if pair_inliers:                                                                            # :46-56
+        _banner('Running image pair inlier scoring ...')
+        start_time = time.time()
+        thr = config.INLIER_THRESHOLD_OPTIONS
+        UndistortImages(cameras, images, device=device)
+        ImagePairInliersCount(view_graph, cameras, images, thr, device=device)
+        FilterInlierNum(view_graph, thr['min_inlier_num'])
+        FilterInlierRatio(view_graph, thr['min_inlier_ratio'])
+        view_graph.keep_largest_connected_component(images)
+        valid = [pair for pair in view_graph.image_pairs.values() if pair.is_valid]
+        trace.append(('pair_inliers', len(valid), int(sum(len(pair.inliers) for pair in valid)), None))
+        T['pair_inliers_s'] = time.time() - start_time
+        print('Image pair inlier scoring took: ', T['pair_inliers_s'])
 
     if not config.OPTIONS['skip_track_establishment']:                                          # :80-91
         _banner('Running track establishment ...')

@@ -635,3 +635,27 @@ def stand_in_rotation_averaging(view_graph, images, scene: MapperScene, rot_sigm
         im.world2cam = np.eye(4)
         im.world2cam[:3, :3] = R[i]
         im.is_registered = True
+
+
+def ground_truth_two_view(view_graph, cameras, images, scene: MapperScene, set_intrinsics=True, config=None):
+    """What relative pose estimation leaves on the pairs of a ``MapperScene`` (global_mapper.py:46-52, out of scope
+    here), from the ground truth: ``rotation`` (xyzw) and unit ``translation`` of x2 ~ R x1 + t, ``E`` = [t]x R and
+    ``F`` = K2^-T E K1^-1 from the cameras' K.  ``config`` overrides every pair's configuration (default: the
+    database's).  ``set_intrinsics`` first writes the ground-truth intrinsics (make_problem's SIMPLE_RADIAL f = 1000,
+    pp = (1000, 750), k = -0.02) into the cameras, so that UndistortImages gives true rays -- the database stores a
+    perturbed focal and no distortion."""
+    if set_intrinsics:
+        for cam in cameras:
+            cam.set_params(np.array([_GT_INTR[2][0], 1000.0, 750.0, _GT_INTR[2][1]]))
+    Kinv = [np.linalg.inv(cam.get_K()) for cam in cameras]
+    for pair in view_graph.image_pairs.values():
+        i1, i2 = pair.image_id1, pair.image_id2
+        R = scene.rot_gt[i2] @ scene.rot_gt[i1].T
+        t = scene.rot_gt[i2] @ (scene.centers_gt[i1] - scene.centers_gt[i2])
+        t = t / np.linalg.norm(t)
+        pair.rotation = _quat_from_matrix(R)
+        pair.translation = t
+        pair.E = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]]) @ R
+        pair.F = Kinv[images[i2].cam_id].T @ pair.E @ Kinv[images[i1].cam_id]
+        if config is not None:
+            pair.config = config

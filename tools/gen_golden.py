@@ -19,6 +19,8 @@ records:
   capturing its input, so nothing past bundle_adjustment.py:132 runs.
 * ``pruning_golden.npz`` (``--only pruning``) -- ``PruneWeaklyConnectedImages`` (reconstruction_pruning.py:172-210) on
   the scenes of tests/pruning_scene.py: the visibility graph in dict order, the threshold, the resulting flags.
+* ``pair_inliers_golden.npz`` (``--only inliers``) -- ``ImagePairInliersCount`` (image_pair_inliers.py:7-133) on the
+  scenes of tests/pair_scene.py: per valid pair the returned score, whether ``inliers`` was assigned, and the inliers.
 
 Only data leaves this script: no reference source is copied into the repository.
 Usage:  python tools/gen_golden.py [--out tests/golden]
@@ -792,10 +794,49 @@ def gen_pruning(out_dir):
           "committed seeds per kind:", {k: len(set(v) & set(PS.SEEDS)) for k, v in kinds.items()})
 
 
+def gen_inliers(out_dir):
+    """ImagePairInliersCount's per-pair work (image_pair_inliers.py:118-125 ``score_error``) on the scenes of
+    tests/pair_scene.py, in the reference's own classes: for every valid pair, in view-graph order, the score it
+    returns, whether it assigned ``pair.inliers`` (the attribute is no longer the object put there before the call),
+    the number of inliers and the inliers themselves, concatenated.  Pairs whose inliers were not assigned contribute
+    a count of 0."""
+    import warnings
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import pair_scene as PS
+    from instantsfm.processors import image_pair_inliers as IP
+    from instantsfm.scene import defs as ref_defs
+    res = {}
+    for name in PS.NAMES:
+        vg, cameras, images = PS.as_objects(PS.scene(name), defs=ref_defs)
+        score, assigned, count, inliers = [], [], [], []
+        for pair in vg.image_pairs.values():
+            if not pair.is_valid:
+                continue
+            before = pair.inliers
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")  # (the zero F divides 0 by 0)
+                score.append(IP.score_error(pair, cameras, images, PS.OPTIONS))
+            assigned.append(pair.inliers is not before)
+            inl = np.asarray(pair.inliers, dtype=np.int64).reshape(-1) if assigned[-1] else np.zeros(0, np.int64)
+            count.append(inl.size)
+            inliers.append(inl)
+        res[f"{name}_score"] = np.array(score, dtype=np.float64)
+        res[f"{name}_assigned"] = np.array(assigned, dtype=bool)
+        res[f"{name}_count"] = np.array(count, dtype=np.int32)
+        res[f"{name}_inliers"] = np.concatenate(inliers).astype(np.uint16)
+        assert max(len(p.matches) for p in vg.image_pairs.values()) < 2 ** 16
+    path = os.path.join(out_dir, "pair_inliers_golden.npz")
+    np.savez_compressed(path, **res)
+    print("pair_inliers_golden.npz", {n: (len(res[f"{n}_score"]), int(res[f"{n}_count"].sum())) for n in PS.NAMES},
+          os.path.getsize(path), "bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", choices=("projection", "packing", "gp", "passes", "retri", "tracks", "depth", "pruning"),
+    ap.add_argument("--only", choices=("projection", "packing", "gp", "passes", "retri", "tracks", "depth", "pruning",
+                                       "inliers"),
                     default=None)
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
@@ -819,6 +860,8 @@ def main():
             gen_depth(args.out)
         if args.only in (None, "pruning"):
             gen_pruning(args.out)
+        if args.only in (None, "inliers"):
+            gen_inliers(args.out)
 
 
 if __name__ == "__main__":
