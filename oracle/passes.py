@@ -10,6 +10,10 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use this mo
   float type) is restated in ``cv_undistort_points``.  PARITY: SIMPLE_PINHOLE / PINHOLE are pinned by golden vectors
   from the reference; the cv2 models are pinned only through the reference's own forward model (``cam2img``, golden
   vectors of it: undistort(cam2img(x)) == x where five iterations converge) -- "parity unpinned" against cv2 itself.
+  The cv2 models' algorithm (the coefficient vector of each model, the five-iteration fixed point, its icdist < 0
+  exit, normal_from_fisheye, the FOV branches and the float32 path) is pinned by tests/passes_reference.py, an
+  independent restatement in mpmath at 50 digits: tests/test_passes_reference.py holds every function of this module
+  to it on wide-field, strongly distorted and branch-by-branch inputs (tests/passes_edge_scene.py).
 * ``filter_reproj_normalized`` -- track_filter.py:26-66 (FilterTracksByReprojectionNormalized), including its
   counter, which tests the slice of the *next* track (``count`` is advanced before the test).  Pinned by golden
   vectors from the reference.
