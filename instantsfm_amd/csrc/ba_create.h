@@ -437,6 +437,8 @@ int setup_two_level(insfm_ba* h, const Clusters& cl, const CoarseLists& co) {
     if ((rc = dd(h, &tl.vc, cd))) return rc;
     if ((rc = dd(h, &tl.Rc, (size_t)m))) return rc;
     if ((rc = dd(h, &tl.gd, 3 * (size_t)C))) return rc;
+    tl.gpref = nullptr;
+    if (h->kind == 1 && (rc = dd(h, &tl.gpref, 3 * (size_t)nc))) return rc;
     {
         int* ip = nullptr;
         if ((rc = upload(h, &ip, cl.lab.data(), cl.lab.size()))) return rc;

@@ -318,7 +318,8 @@ int64_t insfm_ba_debug_get(insfm_ba* h, int32_t which, double* host) {
     const double* src = nullptr;
     size_t n = 0;
     switch (which) {
-        case 0: src = h->W; n = Nl * D * 3; break;
+        // (global positioning keeps its 32-byte {u, beta^2} records at the front of the same buffer: [N,4])
+        case 0: src = h->W; n = h->kind == 1 ? Nl * 4 : Nl * D * 3; break;
         case 1: src = h->V; n = Pl * 6; break;
         case 2: src = h->gp; n = Pl * 3; break;
         case 3: src = h->U; n = C * D * D; break;

@@ -170,6 +170,10 @@ int run_linearize(insfm_ba* h, const double* cams, const double* pts_local) {
 int run_tl_basis(insfm_ba* h, const double* cams, hipStream_t stream) {
     const int C = h->C;
     if (h->kind == 1) {
+        if (h->ss.tl_solves == 0) {  // the first two-level solve since create / reset fixes the scale column's origin
+            k_gp_tl_ref<<<cdiv(h->tl.nc, kThreads), kThreads, 0, stream>>>(cams, h->tl);
+            if (int rc = launch_err(h, "k_gp_tl_ref")) return rc;
+        }
         k_tl_basis<kGP><<<h->tl.nc, kThreads, 0, stream>>>(C, cams, h->Lf, h->tl, h->cg.r[0]);
         return launch_err(h, "k_tl_basis");
     }

@@ -52,6 +52,7 @@ struct TlBufs {
     double* Einv;        // [m][m] compact E^-1 (k_tl_pc reads its cluster's rows)
     double* Ed;          // [ldE] 1 / sqrt(E_kk) (pad: 1): E is inverted as diag(Ed) E diag(Ed) (symmetric equilibration)
     int* ok;             // coarse correction usable (E positive definite)
+    double* gpref;       // [nc][3] global positioning: where each cluster's first camera stood at the first two-level solve
     const int* cl_ptr;   // [nc+1]
     const int* cl_cams;  // cluster members, ascending camera id
     const int* cpos;     // [C] position of camera i in cl_cams
@@ -80,6 +81,14 @@ __device__ __forceinline__ double ld_sc1(const double* p) { return __hip_atomic_
 template <int M>
 __device__ __forceinline__ void tl_basis_entry(int i, int k, const double* __restrict__ cams, const double* __restrict__ Lf,
                                                const TlBufs& tl, const double* __restrict__ r0);
+
+// Global positioning: the reference points of the scale column (tl.gpref), one thread per cluster.
+__global__ __launch_bounds__(kThreads) void k_gp_tl_ref(const double* __restrict__ cams, TlBufs tl) {
+    const int c = blockIdx.x * kThreads + threadIdx.x;
+    if (c >= tl.nc) return;
+    const double* cp = cams + 3 * (size_t)tl.cl_cams[tl.cl_ptr[c]];
+    tl.gpref[3 * (size_t)c] = cp[0]; tl.gpref[3 * (size_t)c + 1] = cp[1]; tl.gpref[3 * (size_t)c + 2] = cp[2];
+}
 
 template <int M>
 __global__ __launch_bounds__(kThreads) void k_tl_basis(int C, const double* __restrict__ cams, const double* __restrict__ Lf,
@@ -151,15 +160,21 @@ __device__ __forceinline__ void tl_basis_entry(int i, int k, const double* __res
                                                const TlBufs& tl, const double* __restrict__ r0) {
     constexpr int D = kD<M>, MC = D + 1, ST = kStride<M>;
     double col[D];
-    if constexpr (M == kGP) {  // global positioning: translation (I) and scaling about the origin (c_i)
+    if constexpr (M == kGP) {
+        // global positioning: translation (I) and scaling about tl.gpref (c_i - ref), where the cluster's first camera
+        // stood at the handle's first two-level solve.  The same span as scaling about the origin, but the column does
+        // not line up with the translations when the scene sits far from the origin (positions ~1e3, extent ~1:
+        // cond(E) ~1e5 and a PCG that breaks down near 1e-12); fixed until insfm_ba_reset, so a lagged E^-1 meets the
+        // basis it was built in
 #pragma unroll
         for (int a = 0; a < D; ++a) col[a] = 0.0;
         if (tl.alone[i]) {
             if (k < D) col[k] = 1.0;
         } else {
             const double* cp = cams + (size_t)i * ST;
+            const double* c0 = tl.gpref + 3 * (size_t)tl.clab[i];
             if (k < 3) col[k] = 1.0;
-            else { col[0] = cp[0]; col[1] = cp[1]; col[2] = cp[2]; }
+            else { col[0] = cp[0] - c0[0]; col[1] = cp[1] - c0[1]; col[2] = cp[2] - c0[2]; }
         }
     } else {
         basis_column<D>(k, cams + (size_t)i * ST, tl.alone[i] != 0, col);

@@ -306,6 +306,7 @@ typedef struct {
     int u_predamped;             /* U already holds the damped camera blocks (global positioning) */
     /* global positioning (TorchGP.Optimize): per obs ray t, factor f, scale-free flag, linearization terms */
     double *gp_t, *gp_f, *gp_beta, *gp_a, *gp_r, *gp_hss, *gp_gs, *gp_ds, *gp_hx, *gp_hc, *gp_gx, *gp_gc;
+    double* gp_ref;              /* [nclust][3] first camera of every cluster at the first two-level solve (coarse_basis) */
     double *gp_scales_new;
     int* gp_sfree;
     int prev_ok, have_prev, fresh_lin;
@@ -487,12 +488,15 @@ int ora_clusters(const ora_t* h, int* lab) {
  *   rho = -R tau - [t]x R omega + sigma t,   phi = -R omega,
  * plus one column per intrinsic.  A camera alone in its cluster gets [I_D | 0] instead (the 7 similarity modes of a
  * single camera are linearly dependent). */
-static void coarse_basis(int D, const double* cam, int alone, double* G, int kind) {
+static void coarse_basis(int D, const double* cam, int alone, double* G, int kind, const double* ref) {
     const int MC = D + 1;
     for (int k = 0; k < D * MC; ++k) G[k] = 0.0;
     if (alone) { for (int a = 0; a < D; ++a) G[a * MC + a] = 1.0; return; }
-    if (kind == 1) {  /* global positioning: camera position c; gauge = translation (I) and scaling about 0 (c) */
-        for (int a = 0; a < 3; ++a) { G[a * MC + a] = 1.0; G[a * MC + 3] = cam[a]; }
+    if (kind == 1) {  /* global positioning: camera position c; gauge = translation (I) and scaling about `ref` (c - ref),
+                       * where the cluster's first camera stood at the handle's first two-level solve: the span of
+                       * scaling about 0, without its near-dependence on the translations when the scene sits far from
+                       * the origin; fixed for the handle's life, so a lagged E^-1 meets the basis it was built in */
+        for (int a = 0; a < 3; ++a) { G[a * MC + a] = 1.0; G[a * MC + 3] = cam[a] - ref[a]; }
         return;
     }
     const double *t = cam, *q = cam + 3;
@@ -643,7 +647,7 @@ void ora_destroy(ora_t* h) {
                     h->r, h->z, h->p, h->q, h->dp, h->cams_new, h->pts_new, h->partial,
                     h->clab, h->csize, h->lin_cams, h->prev_einv, h->gp_t, h->gp_f, h->gp_beta, h->gp_a,
                     h->gp_r, h->gp_hss, h->gp_gs, h->gp_ds, h->gp_hx, h->gp_hc, h->gp_gx, h->gp_gc,
-                    h->gp_scales_new, h->gp_sfree};
+                    h->gp_scales_new, h->gp_sfree, h->gp_ref};
     for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i) free(ptrs[i]);
     free(h);
 }
@@ -966,9 +970,14 @@ static int gj_inverse(int m, double* A) {
 static int ora_coarse_setup(ora_t* h, const double* Lfac, double* Zt, double* Einv) {
     const int D = h->D, C = h->C, MC = D + 1, nc = h->nclust, m = nc * MC;
     const size_t DD = (size_t)D * D;
+    if (h->kind == 1 && !h->gp_ref) {
+        h->gp_ref = (double*)malloc(sizeof(double) * 3 * (size_t)(nc > 0 ? nc : 1));
+        for (int i = C - 1; i >= 0; --i) memcpy(h->gp_ref + 3 * (size_t)h->clab[i], h->lin_cams + (size_t)i * h->stride, sizeof(double) * 3);
+    }
     for (int i = 0; i < C; ++i) {
         double G[MAXD * (MAXD + 1)];
-        coarse_basis(D, h->lin_cams + (size_t)i * h->stride, h->csize[h->clab[i]] < 2, G, h->kind);
+        coarse_basis(D, h->lin_cams + (size_t)i * h->stride, h->csize[h->clab[i]] < 2, G, h->kind,
+                     h->kind == 1 ? h->gp_ref + 3 * (size_t)h->clab[i] : NULL);
         const double* L = Lfac + (size_t)i * DD;
         double* Z = Zt + (size_t)i * D * MC;
         for (int a = 0; a < D; ++a)

@@ -257,8 +257,8 @@ class OracleGP:
         self.D = 3
         dopt = np.array([o['huber_delta'], o['tr_radius'], o['tr_max'], o['tr_min'], o['tr_up'], o['tr_down'],
                          o['tr_factor'], o['tr_high'], o['tr_low'], o['clamp_min'], o['clamp_max'], o['pcg_tol']])
-        iopt = np.array([o['max_rejects'], o['pcg_max_iter'], 1, o['threads'], o['precond'], o['cluster_size'], 0, 0],
-                        np.int32)
+        iopt = np.array([o['max_rejects'], o['pcg_max_iter'], 1, o['threads'], o['precond'], o['cluster_size'],
+                         o['order_seed'], o['order_mode']], np.int32)
         self.h = self.L.ora_gp_create(self.C, self.P, self.N, _d(self.t), _i(self.cam), _i(self.pt), _d(self.fcam),
                                      _i(self.sfree), _d(dopt), _i(iopt))
         if not self.h:
