@@ -6,29 +6,29 @@
 //                      off[t] + i*L - i(i+1)/2 + (j-i-1) (integer only; no inversion of the triangular index), the
 //                      all-ones sentinel for a pair of equal images, and the ordinal itself as the value;
 //   3. radix sort (stable) of (key, ordinal) -- every run of equal keys starts with its smallest ordinal;
-//   4. k_heads + scan + k_starts -- run starts; k_keep + scan + k_emit -- the runs of length >= min_count, the
-//      sentinel run dropped, compacted in key order.
+//   4. k_heads + scan + k_starts (stage_device.h segment_runs) -- run starts; k_keep + scan + k_emit -- the runs of
+//      length >= min_count, the sentinel run dropped, compacted in key order.
 // Image ids are only ever compared and packed, never used as an index, so no bound on them is needed.
-// Scratch comes from the stream-ordered allocator and is released before the call returns: 32 bytes per ordinal
-// (two key and two value buffers, run starts, output positions; head flags and their scan reuse the unsorted key
-// buffer, the keep flags the unsorted values), 16 bytes per track, and hipcub's temporary storage.
+// Scratch and the pinned words the counts come back through belong to one StageTemps (stage_device.h), released
+// before the call returns (also an early one): 32 bytes per ordinal (two key and two value buffers, run starts, output
+// positions; head flags and their scan reuse the unsorted key buffer, the keep flags the unsorted values), 16 bytes per
+// track, and hipcub's temporary storage.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <cstdint>
-#include <vector>
 
 #include "../../include/insfm_ba.h"
 #include "../../include/insfm_covis.h"
 #include "../../include/insfm_tracks.h"
+#include "stage_device.h"
 
 namespace {
 
-constexpr int kT = 256;
+using namespace insfm;
+
 constexpr int64_t kMaxItems = (int64_t)1 << 31;  // hipcub item counts are int
 constexpr unsigned long long kSame = ~0ull;      // key of a pair whose two rows name one image
-
-inline unsigned grid(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
 
 // A track longer than 65536 rows alone has 2^31 ordinals or more: its count saturates at 2^31 (the call is then
 // refused) so that the int64 sum over fewer than 2^31 tracks cannot overflow.
@@ -68,21 +68,6 @@ __global__ __launch_bounds__(kT) void k_expand(int64_t nt, int64_t n_rows, const
     }
 }
 
-__global__ __launch_bounds__(kT) void k_heads(int64_t n, const unsigned long long* __restrict__ key, int* __restrict__ head) {
-    const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-    if (i >= n) return;
-    head[i] = (i == 0 || key[i] != key[i - 1]) ? 1 : 0;
-}
-
-// start[run] = first element of the run (incl = inclusive scan of the heads); start[runs] = n.
-__global__ __launch_bounds__(kT) void k_starts(int64_t n, const int* __restrict__ head, const int* __restrict__ incl,
-                                               int* __restrict__ start) {
-    const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-    if (i >= n) return;
-    if (head[i]) start[incl[i] - 1] = (int)i;
-    if (i == n - 1) start[incl[i]] = (int)n;
-}
-
 __global__ __launch_bounds__(kT) void k_keep(int nr, const int* __restrict__ start, const unsigned long long* __restrict__ skey,
                                              int min_count, int* __restrict__ keep) {
     const int r = blockIdx.x * kT + threadIdx.x;
@@ -106,26 +91,6 @@ __global__ __launch_bounds__(kT) void k_emit(int nr, const int* __restrict__ sta
     pair_first[q] = sval[s];
 }
 
-struct Scratch {
-    hipStream_t s;
-    std::vector<void*> ptrs;
-    bool ok = true;
-    template <typename T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        if (hipMallocAsync(&p, (n ? n : 1) * sizeof(T), s) != hipSuccess) {
-            ok = false;
-            return nullptr;
-        }
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-    ~Scratch() {
-        for (void* p : ptrs) (void)hipFreeAsync(p, s);
-        (void)hipStreamSynchronize(s);
-    }
-};
-
 }  // namespace
 
 extern "C" int insfm_covis_pairs(int64_t n_tracks, const int64_t* track_ptr, const int32_t* obs_img, int32_t min_count,
@@ -138,31 +103,27 @@ extern "C" int insfm_covis_pairs(int64_t n_tracks, const int64_t* track_ptr, con
     if (!track_ptr || !obs_img) return INSFM_BA_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t nt = n_tracks;
-    Scratch w{s};
+    StageTemps w(s);
     int64_t* cnt = w.get<int64_t>(nt);
     int64_t* off = w.get<int64_t>(nt);
     int* bad = w.get<int>(1);
-    int64_t* host = nullptr;
-    if (!w.ok || hipHostMalloc(reinterpret_cast<void**>(&host), 8 * sizeof(int64_t)) != hipSuccess) return INSFM_BA_ENOMEM;
-    struct HostFree {
-        int64_t* p;
-        ~HostFree() { (void)hipHostFree(p); }
-    } host_guard{host};
-    int* hosti = reinterpret_cast<int*>(host + 4);
+    if (!w.ok()) return INSFM_BA_ENOMEM;
+    int64_t* host = w.host();
+    int* hosti = w.hosti();
 
     size_t b = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, cnt, off, (int)nt, s);
+    INSFM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, cnt, off, (int)nt, s));
     void* tmp0 = w.get<unsigned char>(b);
-    if (!w.ok) return INSFM_BA_ENOMEM;
-    (void)hipMemsetAsync(bad, 0, sizeof(int), s);
-    k_track_pairs<<<grid(nt), kT, 0, s>>>(nt, track_ptr, cnt, bad);
-    (void)hipcub::DeviceScan::ExclusiveSum(tmp0, b, cnt, off, (int)nt, s);
-    (void)hipMemcpyAsync(host, off + nt - 1, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(host + 1, cnt + nt - 1, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(host + 2, track_ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(host + 3, track_ptr + nt, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(hosti, bad, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return INSFM_BA_EHIP;
+    if (!w.ok()) return INSFM_BA_ENOMEM;
+    INSFM_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+    launch(k_track_pairs, nt, s, nt, track_ptr, cnt, bad);
+    INSFM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp0, b, cnt, off, (int)nt, s));
+    INSFM_HIP(hipMemcpyAsync(host, off + nt - 1, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(hipMemcpyAsync(host + 1, cnt + nt - 1, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(hipMemcpyAsync(host + 2, track_ptr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(hipMemcpyAsync(host + 3, track_ptr + nt, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(hipMemcpyAsync(hosti, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(settle(s));
     if (hosti[0]) return INSFM_BA_EINVAL;
     const int64_t total = host[0] + host[1], n_rows = host[3] - host[2];
     counts[1] = total;
@@ -179,37 +140,28 @@ extern "C" int insfm_covis_pairs(int64_t n_tracks, const int64_t* track_ptr, con
     int* head = reinterpret_cast<int*>(key);  // the unsorted keys are dead after the sort: 2 ints per key
     int* incl = head + total;
     int* keep = val;                          // and so are the unsorted values
-    size_t tmp_bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, key, skey, val, sval, (int)total, 0, 64, s);
-    tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, head, incl, (int)total, s);
-    tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, keep, pos, (int)total, s);
-    tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
+    TempBytes need;
+    INSFM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need.next(), key, skey, val, sval, (int)total, 0, 64, s));
+    INSFM_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, need.next(), head, incl, (int)total, s));
+    INSFM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need.next(), keep, pos, (int)total, s));
+    const size_t tmp_bytes = need.bytes();
     void* tmp = w.get<unsigned char>(tmp_bytes);
-    if (!w.ok) return INSFM_BA_ENOMEM;
+    if (!w.ok()) return INSFM_BA_ENOMEM;
 
-    k_expand<<<grid(n_rows), kT, 0, s>>>(nt, n_rows, track_ptr, off, obs_img, total, key, val);
-    b = tmp_bytes;
-    (void)hipcub::DeviceRadixSort::SortPairs(tmp, b, key, skey, val, sval, (int)total, 0, 64, s);
-    k_heads<<<grid(total), kT, 0, s>>>(total, skey, head);
-    b = tmp_bytes;
-    (void)hipcub::DeviceScan::InclusiveSum(tmp, b, head, incl, (int)total, s);
-    k_starts<<<grid(total), kT, 0, s>>>(total, head, incl, start);
-    (void)hipMemcpyAsync(hosti, incl + total - 1, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return INSFM_BA_EHIP;
-    const int nr = hosti[0];
+    launch(k_expand, n_rows, s, nt, n_rows, track_ptr, off, obs_img, total, key, val);
+    INSFM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, b = tmp_bytes, key, skey, val, sval, (int)total, 0, 64, s));
+    int nr = 0;
+    if (int rc = segment_runs(w, tmp, tmp_bytes, (int)total, skey, head, incl, start, &nr)) return rc;
 
-    k_keep<<<grid(nr), kT, 0, s>>>(nr, start, skey, min_count, keep);
-    b = tmp_bytes;
-    (void)hipcub::DeviceScan::ExclusiveSum(tmp, b, keep, pos, nr, s);
-    (void)hipMemcpyAsync(hosti, pos + nr - 1, sizeof(int), hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(hosti + 1, keep + nr - 1, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return INSFM_BA_EHIP;
+    launch(k_keep, nr, s, nr, start, skey, min_count, keep);
+    INSFM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, b = tmp_bytes, keep, pos, nr, s));
+    INSFM_HIP(hipMemcpyAsync(hosti, pos + nr - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(hipMemcpyAsync(hosti + 1, keep + nr - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(settle(s));
     const int64_t n_out = (int64_t)hosti[0] + hosti[1];
     if (n_out > capacity) return INSFM_BA_EINVAL;  // before anything is written
-    k_emit<<<grid(nr), kT, 0, s>>>(nr, start, keep, pos, skey, sval, pair_lo, pair_hi, pair_count, pair_first);
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return INSFM_BA_EHIP;
+    launch(k_emit, nr, s, nr, start, keep, pos, skey, sval, pair_lo, pair_hi, pair_count, pair_first);
+    INSFM_HIP(settle(s));
     counts[0] = n_out;
     return INSFM_BA_OK;
 }

@@ -8,7 +8,9 @@
 //      fixed order at the end (no atomics: the bytes are the same from run to run).  The fundamental kind walks twice:
 //      the first walk counts the orientation votes of the pre-inliers, the second recomputes each match and selects
 //      the majority side, so nothing is stashed in the output and a tied pair writes no index at all.
-// The per-pair constants (32 doubles) are read at a wave-uniform address; no LDS, no scratch buffers besides the flag.
+// The per-pair constants (32 doubles) are read at a wave-uniform address; no LDS, no scratch buffers besides the flag
+// word, which a StageTemps (stage_device.h) owns.  The word is read back into a local, not a pinned block: the call
+// takes 0.5 ms, and allocating and freeing pinned memory would add 0.2 ms to it.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -16,16 +18,16 @@
 #include "../../include/insfm_ba.h"
 #include "../../include/insfm_pairs.h"
 #include "../../include/insfm_tracks.h"
+#include "stage_device.h"
 
 namespace {
 
-constexpr int kT = 256;
+using namespace insfm;
+
 constexpr int kWaves = kT / 64;
 constexpr int kG = INSFM_PAIR_GEOM_STRIDE;
 constexpr double kEps = 1e-10;  // EPSILON of two_view_geometry.py:4
 constexpr int kBadPtr = 1, kBadKind = 2, kBadMatch = 4, kHasEssential = 8;
-
-inline unsigned grid(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 __global__ __launch_bounds__(kT) void k_check_pairs(int64_t np, int64_t nm, const int64_t* __restrict__ ptr,
                                                     const int32_t* __restrict__ kind, int* __restrict__ flags) {
@@ -58,12 +60,9 @@ __device__ inline V3 row(const double* g, int i) { return {g[3 * i], g[3 * i + 1
 __device__ inline V3 col(const double* g, int j) { return {g[j], g[3 + j], g[6 + j]}; }
 
 __device__ inline V3 pixel(const void* xy, int f32, int64_t i) {
-    if (f32) {
-        const float* p = static_cast<const float*>(xy) + 2 * i;
-        return {(double)p[0], (double)p[1], 1.0};
-    }
-    const double* p = static_cast<const double*>(xy) + 2 * i;
-    return {p[0], p[1], 1.0};
+    V3 p = {0.0, 0.0, 1.0};
+    load_xy(xy, f32, i, p.x, p.y);
+    return p;
 }
 
 __device__ inline V3 ray(const void* rays, int f32, int64_t i) {
@@ -222,27 +221,19 @@ extern "C" int insfm_pair_inliers(int64_t n_pairs, const int64_t* pair_ptr, int6
     if (!pair_ptr || !pair_kind || !pair_geom || !inlier_count || !score || !touched) return INSFM_BA_EINVAL;
     if (n_matches > 0 && (!match_a || !match_b || !xy || !inlier_idx || n_features == 0)) return INSFM_BA_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int* flags = nullptr;
-    if (hipMallocAsync(reinterpret_cast<void**>(&flags), sizeof(int), s) != hipSuccess) return INSFM_BA_ENOMEM;
-    struct Free {
-        int* p;
-        hipStream_t s;
-        ~Free() {
-            (void)hipFreeAsync(p, s);
-            (void)hipStreamSynchronize(s);
-        }
-    } guard{flags, s};
     int host_flags = 0;
-    (void)hipMemsetAsync(flags, 0, sizeof(int), s);
-    k_check_pairs<<<grid(n_pairs, kT), kT, 0, s>>>(n_pairs, n_matches, pair_ptr, pair_kind, flags);
-    if (n_matches > 0) k_check_matches<<<grid(n_matches, kT), kT, 0, s>>>(n_matches, n_features, match_a, match_b, flags);
-    (void)hipMemcpyAsync(&host_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return INSFM_BA_EHIP;
+    StageTemps w(s, /*pinned=*/false);
+    int* flags = w.get<int>(1);
+    if (!w.ok()) return INSFM_BA_ENOMEM;
+    INSFM_HIP(hipMemsetAsync(flags, 0, sizeof(int), s));
+    launch(k_check_pairs, n_pairs, s, n_pairs, n_matches, pair_ptr, pair_kind, flags);
+    launch(k_check_matches, n_matches, s, n_matches, n_features, match_a, match_b, flags);
+    INSFM_HIP(hipMemcpyAsync(&host_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(settle(s));
     if (host_flags & (kBadPtr | kBadKind | kBadMatch)) return INSFM_BA_EINVAL;
     if ((host_flags & kHasEssential) && !rays) return INSFM_BA_EINVAL;
-    k_pair_inliers<<<grid(n_pairs, kWaves), kT, 0, s>>>(n_pairs, pair_ptr, match_a, match_b, xy, xy_f32, rays,
-                                                        rays_f32, pair_kind, pair_geom, inlier_idx, inlier_count,
-                                                        score, touched);
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return INSFM_BA_EHIP;
+    launch<kWaves>(k_pair_inliers, n_pairs, s, n_pairs, pair_ptr, match_a, match_b, xy, xy_f32, rays, rays_f32, pair_kind,
+                   pair_geom, inlier_idx, inlier_count, score, touched);
+    INSFM_HIP(settle(s));
     return INSFM_BA_OK;
 }

@@ -13,11 +13,22 @@
 #pragma clang fp contract(off)
 
 #include "ba_device.h"  // eval_obs<M>: the reproject_funcs restatement shared with the BA kernels
+#include "stage_device.h"  // launch, load_xy, the checked-call form
 
 namespace {
 
-constexpr int kT = 256;
+using namespace insfm;
+
 constexpr double kEps = 1e-10;
+
+// p = world2cam[:3, :] [X, 1] for a row-major 4x4 W, every row rounded as ((W0 X0 + W1 X1) + W2 X2) + W3: the order of
+// numpy's einsum and of `R @ X + t` alike.  Stays in this file, below the contraction pragma.
+__device__ __forceinline__ void cam_point(const double* W, const double* X, double& p0, double& p1, double& p2) {
+    const double X0 = X[0], X1 = X[1], X2 = X[2];
+    p0 = W[0] * X0 + W[1] * X1 + W[2] * X2 + W[3];
+    p1 = W[4] * X0 + W[5] * X1 + W[6] * X2 + W[7];
+    p2 = W[8] * X0 + W[9] * X1 + W[10] * X2 + W[11];
+}
 
 // cvUndistortPointsInternal (OpenCV 4.10, calib3d/src/undistort.dispatch.cpp) for R = I, no tilt, default criteria
 // COUNT 5: fixed-point iteration x <- (x0 - delta(x)) * icdist(x) on the K-normalized point.
@@ -130,15 +141,7 @@ __global__ __launch_bounds__(kT) void k_undistort(int64_t n, const void* __restr
     const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
     if (i >= n) return;
     double u, v;
-    if (f32) {
-        const float2 q = reinterpret_cast<const float2*>(xy)[i];
-        u = q.x;
-        v = q.y;
-    } else {
-        const double2 q = reinterpret_cast<const double2*>(xy)[i];
-        u = q.x;
-        v = q.y;
-    }
+    load_xy(xy, f32, i, u, v);
     const int c = feat_cam[i];
     double x, y;
     img2cam(cam_model[c], cam_params + 12 * (size_t)c, u, v, f32 != 0, x, y);
@@ -159,11 +162,8 @@ __global__ __launch_bounds__(kT) void k_filter_reproj(int64_t n, const int32_t* 
     const double* W = w2c + 16 * (size_t)obs_img[x];
     const double* X = xyz + 3 * (size_t)obs_track[x];
     const double* r = rays + 3 * obs_ray[x];
-    const double X0 = X[0], X1 = X[1], X2 = X[2];
-    // einsum('ijk,ik->ij', world2cam, [xyz, 1])[:, :3]
-    const double p0 = W[0] * X0 + W[1] * X1 + W[2] * X2 + W[3];
-    const double p1 = W[4] * X0 + W[5] * X1 + W[6] * X2 + W[7];
-    const double p2 = W[8] * X0 + W[9] * X1 + W[10] * X2 + W[11];
+    double p0, p1, p2;  // einsum('ijk,ik->ij', world2cam, [xyz, 1])[:, :3]
+    cam_point(W, X, p0, p1, p2);
     const double rz = r[2] + kEps, pz = p2 + kEps;
     const double d0 = p0 / pz - r[0] / rz, d1 = p1 / pz - r[1] / rz;
     const double e = sqrt(d0 * d0 + d1 * d1);
@@ -181,10 +181,8 @@ __global__ __launch_bounds__(kT) void k_filter_angle(int64_t n, const int32_t* _
     const double* W = w2c + 16 * (size_t)obs_img[x];
     const double* X = xyz + 3 * (size_t)obs_track[x];
     const double* r = rays + 3 * obs_ray[x];
-    // world2cam[:3, :3] @ xyz + world2cam[:3, 3]
-    const double p0 = (W[0] * X[0] + W[1] * X[1] + W[2] * X[2]) + W[3];
-    const double p1 = (W[4] * X[0] + W[5] * X[1] + W[6] * X[2]) + W[7];
-    const double p2 = (W[8] * X[0] + W[9] * X[1] + W[10] * X[2]) + W[11];
+    double p0, p1, p2;  // world2cam[:3, :3] @ xyz + world2cam[:3, 3]
+    cam_point(W, X, p0, p1, p2);
     if (p2 < kEps) { valid[x] = 0; return; }
     const double nrm = sqrt(p0 * p0 + p1 * p1 + p2 * p2);
     const double dot = (p0 / nrm) * r[0] + (p1 / nrm) * r[1] + (p2 / nrm) * r[2];
@@ -304,21 +302,13 @@ __global__ __launch_bounds__(kT) void k_filter_reproj_pixel(int64_t n, const int
     const int im = obs_img[x];
     const double* W = w2c + 16 * (size_t)im;
     const double* X = xyz + 3 * (size_t)obs_track[x];
-    const double X0 = X[0], X1 = X[1], X2 = X[2];
-    const double p0 = W[0] * X0 + W[1] * X1 + W[2] * X2 + W[3];
-    const double p1 = W[4] * X0 + W[5] * X1 + W[6] * X2 + W[7];
-    const double p2 = W[8] * X0 + W[9] * X1 + W[10] * X2 + W[11];
+    double p0, p1, p2;
+    cam_point(W, X, p0, p1, p2);
     const int c = img_cam[im];
     double px, py;
     cam2img(cam_model[c], cam_params + 12 * (size_t)c, p0, p1, p2, px, py);
     double fu, fv;
-    if (f32) {
-        const float2 q = reinterpret_cast<const float2*>(feats)[obs_feat[x]];
-        fu = q.x; fv = q.y;
-    } else {
-        const double2 q = reinterpret_cast<const double2*>(feats)[obs_feat[x]];
-        fu = q.x; fv = q.y;
-    }
+    load_xy(feats, f32, obs_feat[x], fu, fv);
     const double d0 = px - fu, d1 = py - fv;
     const double e = sqrt(d0 * d0 + d1 * d1);
     valid[x] = (p2 > kEps) && (e < max_err);
@@ -346,13 +336,7 @@ __global__ __launch_bounds__(kT) void k_reproj_candidates(int64_t n, const int32
                           xyz[3 * (size_t)cand_track[x] + 2]};
     const double pp[2] = {pps[2 * (size_t)im], pps[2 * (size_t)im + 1]};
     double uv[2];
-    if (f32) {
-        const float2 q = reinterpret_cast<const float2*>(feats)[cand_feat[x]];
-        uv[0] = q.x; uv[1] = q.y;
-    } else {
-        const double2 q = reinterpret_cast<const double2*>(feats)[cand_feat[x]];
-        uv[0] = q.x; uv[1] = q.y;
-    }
+    load_xy(feats, f32, cand_feat[x], uv[0], uv[1]);
     double r[2];
     insfm::eval_obs<M, false>(cam, Xp, pp, uv, r, nullptr, nullptr);
     // rotate_quat z (the same expression eval_obs evaluates)
@@ -366,23 +350,18 @@ __global__ __launch_bounds__(kT) void k_reproj_candidates(int64_t n, const int32
     if (err_out) err_out[x] = e;
 }
 
-inline unsigned grid(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
-
-int finish() {
-    return hipGetLastError() == hipSuccess ? INSFM_BA_OK : INSFM_BA_EHIP;
-}
-
 }  // namespace
 
+// The passes only queue their kernel: each ends with the launch-error check, the caller synchronises.
 extern "C" {
 
 int insfm_undistort(int64_t n, const void* xy, int32_t xy_f32, const int32_t* feat_cam, const int32_t* cam_model,
                     const double* cam_params, double* rays, void* stream) {
     if (n < 0 || (n > 0 && (!xy || !feat_cam || !cam_model || !cam_params || !rays))) return INSFM_BA_EINVAL;
     if (n == 0) return INSFM_BA_OK;
-    k_undistort<<<grid(n), kT, 0, reinterpret_cast<hipStream_t>(stream)>>>(n, xy, xy_f32, feat_cam, cam_model, cam_params,
-                                                                         rays);
-    return finish();
+    launch(k_undistort, n, reinterpret_cast<hipStream_t>(stream), n, xy, xy_f32, feat_cam, cam_model, cam_params, rays);
+    INSFM_HIP(hipGetLastError());
+    return INSFM_BA_OK;
 }
 
 int insfm_filter_reproj_normalized(int64_t n_obs, const int32_t* obs_img, const int32_t* obs_track, const int64_t* obs_ray,
@@ -391,10 +370,10 @@ int insfm_filter_reproj_normalized(int64_t n_obs, const int32_t* obs_img, const 
     if (n_obs < 0 || (n_obs > 0 && (!obs_img || !obs_track || !obs_ray || !world2cam || !track_xyz || !rays || !valid)))
         return INSFM_BA_EINVAL;
     if (n_obs == 0) return INSFM_BA_OK;
-    k_filter_reproj<<<grid(n_obs), kT, 0, reinterpret_cast<hipStream_t>(stream)>>>(n_obs, obs_img, obs_track, obs_ray,
-                                                                                  world2cam, track_xyz, rays, max_err, valid,
-                                                                                  err);
-    return finish();
+    launch(k_filter_reproj, n_obs, reinterpret_cast<hipStream_t>(stream), n_obs, obs_img, obs_track, obs_ray, world2cam,
+           track_xyz, rays, max_err, valid, err);
+    INSFM_HIP(hipGetLastError());
+    return INSFM_BA_OK;
 }
 
 int insfm_filter_angle(int64_t n_obs, const int32_t* obs_img, const int32_t* obs_track, const int64_t* obs_ray,
@@ -403,9 +382,10 @@ int insfm_filter_angle(int64_t n_obs, const int32_t* obs_img, const int32_t* obs
     if (n_obs < 0 || (n_obs > 0 && (!obs_img || !obs_track || !obs_ray || !world2cam || !track_xyz || !rays || !valid)))
         return INSFM_BA_EINVAL;
     if (n_obs == 0) return INSFM_BA_OK;
-    k_filter_angle<<<grid(n_obs), kT, 0, reinterpret_cast<hipStream_t>(stream)>>>(n_obs, obs_img, obs_track, obs_ray,
-                                                                                 world2cam, track_xyz, rays, cos_thres, valid);
-    return finish();
+    launch(k_filter_angle, n_obs, reinterpret_cast<hipStream_t>(stream), n_obs, obs_img, obs_track, obs_ray, world2cam,
+           track_xyz, rays, cos_thres, valid);
+    INSFM_HIP(hipGetLastError());
+    return INSFM_BA_OK;
 }
 
 int insfm_filter_tri_angle(int64_t n_tracks, const int64_t* track_ptr, const int32_t* obs_img, const double* centers,
@@ -413,9 +393,10 @@ int insfm_filter_tri_angle(int64_t n_tracks, const int64_t* track_ptr, const int
     if (n_tracks < 0 || (n_tracks > 0 && (!track_ptr || !obs_img || !centers || !track_xyz || !remove)))
         return INSFM_BA_EINVAL;
     if (n_tracks == 0) return INSFM_BA_OK;
-    k_filter_tri_angle<<<grid(n_tracks), kT, 0, reinterpret_cast<hipStream_t>(stream)>>>(n_tracks, track_ptr, obs_img,
-                                                                                        centers, track_xyz, cos_thres, remove);
-    return finish();
+    launch(k_filter_tri_angle, n_tracks, reinterpret_cast<hipStream_t>(stream), n_tracks, track_ptr, obs_img, centers,
+           track_xyz, cos_thres, remove);
+    INSFM_HIP(hipGetLastError());
+    return INSFM_BA_OK;
 }
 
 int insfm_filter_reproj_pixel(int64_t n_obs, const int32_t* obs_img, const int32_t* obs_track, const int64_t* obs_feat,
@@ -426,10 +407,10 @@ int insfm_filter_reproj_pixel(int64_t n_obs, const int32_t* obs_img, const int32
                                     !world2cam || !track_xyz || !valid)))
         return INSFM_BA_EINVAL;
     if (n_obs == 0) return INSFM_BA_OK;
-    k_filter_reproj_pixel<<<grid(n_obs), kT, 0, reinterpret_cast<hipStream_t>(stream)>>>(
-        n_obs, obs_img, obs_track, obs_feat, feats, feats_f32, img_cam, cam_model, cam_params, world2cam, track_xyz, max_err,
-        valid, err);
-    return finish();
+    launch(k_filter_reproj_pixel, n_obs, reinterpret_cast<hipStream_t>(stream), n_obs, obs_img, obs_track, obs_feat, feats,
+           feats_f32, img_cam, cam_model, cam_params, world2cam, track_xyz, max_err, valid, err);
+    INSFM_HIP(hipGetLastError());
+    return INSFM_BA_OK;
 }
 
 int insfm_reproj_candidates(int64_t n, int32_t cam_model, const int32_t* cand_img, const int32_t* cand_track,
@@ -440,11 +421,10 @@ int insfm_reproj_candidates(int64_t n, int32_t cam_model, const int32_t* cand_im
                             !valid)))
         return INSFM_BA_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define INSFM_CAND(M)                                                                                                      \
-    case M:                                                                                                                \
-        if (n > 0)                                                                                                         \
-            k_reproj_candidates<M><<<grid(n), kT, 0, s>>>(n, cand_img, cand_track, cand_feat, feats, feats_f32, image_rows, \
-                                                          image_pps, track_xyz, max_err, valid, err);                      \
+#define INSFM_CAND(M)                                                                                                     \
+    case M:                                                                                                               \
+        launch(k_reproj_candidates<M>, n, s, n, cand_img, cand_track, cand_feat, feats, feats_f32, image_rows, image_pps, \
+               track_xyz, max_err, valid, err);                                                                           \
         break;
     switch (cam_model) {
         INSFM_CAND(0) INSFM_CAND(1) INSFM_CAND(2) INSFM_CAND(3) INSFM_CAND(4) INSFM_CAND(5) INSFM_CAND(6) INSFM_CAND(8)
@@ -452,7 +432,9 @@ int insfm_reproj_candidates(int64_t n, int32_t cam_model, const int32_t* cand_im
         default: return INSFM_BA_EINVAL;  // FOV / THIN_PRISM_FISHEYE: reproject_funcs raises (cost_function.py:125,179)
     }
 #undef INSFM_CAND
-    return n > 0 ? finish() : INSFM_BA_OK;
+    if (n == 0) return INSFM_BA_OK;
+    INSFM_HIP(hipGetLastError());
+    return INSFM_BA_OK;
 }
 
 }  // extern "C"

@@ -12,24 +12,24 @@
 //   6. k_entries + scan -- the distinct observations of each component in order of first appearance;
 //   7. k_row_key + radix sort (stable) -- observations grouped by (component, image), first appearance inside;
 //   8. k_rows       -- per (component, image): inconsistency test over the group's pairs and the kept observation.
-// Scratch comes from the stream-ordered allocator and is released before the call returns.
+// k_heads, k_starts and the run segmentation that steps 4 and 7 end in are stage_device.h's.  Scratch and the pinned
+// words the counts come back through belong to one StageTemps, released before the call returns (also an early one).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <cstdint>
-#include <vector>
 
 #include "../../include/insfm_ba.h"
 #include "../../include/insfm_tracks.h"
+#include "stage_device.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kT = 256;
-constexpr int kNone = 0x7fffffff;
+using namespace insfm;
 
-inline unsigned grid(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
+constexpr int kNone = 0x7fffffff;
 
 __device__ __forceinline__ int ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -106,22 +106,6 @@ __global__ __launch_bounds__(kT) void k_edge_key(int64_t ne, const int32_t* __re
     if (k >= ne) return;
     key[k] = first_edge[label[ea[k]]];
     val[k] = (int)k;
-}
-
-template <typename K>
-__global__ __launch_bounds__(kT) void k_heads(int64_t n, const K* __restrict__ key, int* __restrict__ head) {
-    const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-    if (i >= n) return;
-    head[i] = (i == 0 || key[i] != key[i - 1]) ? 1 : 0;
-}
-
-// seg[i] = inclusive scan of heads - 1 = segment of element i; start[seg] = i at heads; start[nseg] = n.
-__global__ __launch_bounds__(kT) void k_starts(int64_t n, const int* __restrict__ head, const int* __restrict__ incl,
-                                               int* __restrict__ start) {
-    const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-    if (i >= n) return;
-    if (head[i]) start[incl[i] - 1] = (int)i;
-    if (i == n - 1) start[incl[i]] = (int)n;
 }
 
 __global__ __launch_bounds__(kT) void k_minus_one(int64_t n, const int* __restrict__ in, int* __restrict__ out) {
@@ -222,32 +206,6 @@ __global__ __launch_bounds__(kT) void k_rows(int ng, const int* __restrict__ gst
     row_track[g] = t;
 }
 
-int bits_for(int64_t n) {
-    int b = 1;
-    while (b < 62 && ((int64_t)1 << b) < n) ++b;
-    return b;
-}
-
-struct Scratch {
-    hipStream_t s;
-    std::vector<void*> ptrs;
-    bool ok = true;
-    template <typename T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        if (hipMallocAsync(&p, (n ? n : 1) * sizeof(T), s) != hipSuccess) {
-            ok = false;
-            return nullptr;
-        }
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-    ~Scratch() {
-        for (void* p : ptrs) (void)hipFreeAsync(p, s);
-        (void)hipStreamSynchronize(s);
-    }
-};
-
 }  // namespace
 
 extern "C" int insfm_tracks_establish(int64_t n_nodes, const int32_t* node_img, const void* node_xy, int32_t xy_f32,
@@ -262,7 +220,7 @@ extern "C" int insfm_tracks_establish(int64_t n_nodes, const int32_t* node_img, 
         return INSFM_BA_EINVAL;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t n = n_nodes, ne = n_edges, nq = 2 * n_edges;
-    Scratch w{s};
+    StageTemps w(s);
     int* par = w.get<int>(n);
     int* par2 = w.get<int>(n);
     int* first_entry = w.get<int>(n);
@@ -282,72 +240,54 @@ extern "C" int insfm_tracks_establish(int64_t n_nodes, const int32_t* node_img, 
     unsigned long long* obs_key = w.get<unsigned long long>(nq);
     unsigned long long* skey64 = w.get<unsigned long long>(nq);
     int* gstart = w.get<int>(nq + 1);
-    int* host = nullptr;
-    if (!w.ok || hipHostMalloc(reinterpret_cast<void**>(&host), 4 * sizeof(int)) != hipSuccess) return INSFM_BA_ENOMEM;
-    struct HostFree {
-        int* p;
-        ~HostFree() { (void)hipHostFree(p); }
-    } host_guard{host};
+    if (!w.ok()) return INSFM_BA_ENOMEM;
+    int* host = w.hosti();
 
     // temp storage for the sorts and scans: the largest requirement of the four shapes
-    size_t tmp_bytes = 0, b = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, key, skey, val, sedge, (int)ne, 0, bits_for(ne), s);
-    tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, obs_key, skey64, obs_node, snode, (int)nq, 0, 64, s);
-    tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, head, incl, (int)nq, s);
-    tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, flag, pos, (int)nq, s);
-    tmp_bytes = b > tmp_bytes ? b : tmp_bytes;
+    TempBytes need;
+    INSFM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need.next(), key, skey, val, sedge, (int)ne, 0, bits_for(ne), s));
+    INSFM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need.next(), obs_key, skey64, obs_node, snode, (int)nq, 0, 64, s));
+    INSFM_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, need.next(), head, incl, (int)nq, s));
+    INSFM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need.next(), flag, pos, (int)nq, s));
+    const size_t tmp_bytes = need.bytes();
     void* tmp = w.get<unsigned char>(tmp_bytes);
-    if (!w.ok) return INSFM_BA_ENOMEM;
+    if (!w.ok()) return INSFM_BA_ENOMEM;
+    size_t b;
 
-    k_init<<<grid(n), kT, 0, s>>>(n, par, par2, first_entry, deg, first_edge);
-    k_link<<<grid(ne), kT, 0, s>>>(ne, edge_a, edge_b, par, first_entry, deg);
-    k_label<<<grid(n), kT, 0, s>>>(n, par);
-    k_first_edge<<<grid(ne), kT, 0, s>>>(ne, edge_a, par, first_edge);
-    k_edge_key<<<grid(ne), kT, 0, s>>>(ne, edge_a, par, first_edge, key, val);
-    b = tmp_bytes;
-    (void)hipcub::DeviceRadixSort::SortPairs(tmp, b, key, skey, val, sedge, (int)ne, 0, bits_for(ne), s);
-    k_heads<int><<<grid(ne), kT, 0, s>>>(ne, skey, head);
-    b = tmp_bytes;
-    (void)hipcub::DeviceScan::InclusiveSum(tmp, b, head, incl, (int)ne, s);
-    k_starts<<<grid(ne), kT, 0, s>>>(ne, head, incl, cstart);
-    (void)hipMemcpyAsync(host, incl + ne - 1, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return INSFM_BA_EHIP;
-    const int nt = host[0];
+    launch(k_init, n, s, n, par, par2, first_entry, deg, first_edge);
+    launch(k_link, ne, s, ne, edge_a, edge_b, par, first_entry, deg);
+    launch(k_label, n, s, n, par);
+    launch(k_first_edge, ne, s, ne, edge_a, par, first_edge);
+    launch(k_edge_key, ne, s, ne, edge_a, par, first_edge, key, val);
+    INSFM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, b = tmp_bytes, key, skey, val, sedge, (int)ne, 0, bits_for(ne), s));
+    int nt = 0;
+    if (int rc = segment_runs(w, tmp, tmp_bytes, (int)ne, skey, head, incl, cstart, &nt)) return rc;
 
-    k_replay<<<grid(nt), kT, 0, s>>>(nt, cstart, sedge, edge_a, edge_b, par2, track_root);
-    (void)hipMemsetAsync(track_bad, 0, (size_t)nt, s);
-    k_entry_flags<<<grid(nq), kT, 0, s>>>(ne, sedge, edge_a, edge_b, first_entry, flag);
-    b = tmp_bytes;
-    (void)hipcub::DeviceScan::ExclusiveSum(tmp, b, flag, pos, (int)nq, s);
+    launch(k_replay, nt, s, nt, cstart, sedge, edge_a, edge_b, par2, track_root);
+    INSFM_HIP(hipMemsetAsync(track_bad, 0, (size_t)nt, s));
+    launch(k_entry_flags, nq, s, ne, sedge, edge_a, edge_b, first_entry, flag);
+    INSFM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, b = tmp_bytes, flag, pos, (int)nq, s));
     // component of grouped edge i: incl[i] - 1
     int* ecomp = val;  // the unsorted edge ids are no longer needed
-    k_minus_one<<<grid(ne), kT, 0, s>>>(ne, incl, ecomp);
-    k_entries<<<grid(nq), kT, 0, s>>>(ne, sedge, edge_a, edge_b, flag, pos, ecomp, node_img, obs_node, obs_key);
-    (void)hipMemcpyAsync(host, pos + nq - 1, sizeof(int), hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(host + 1, flag + nq - 1, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return INSFM_BA_EHIP;
+    launch(k_minus_one, ne, s, ne, incl, ecomp);
+    launch(k_entries, nq, s, ne, sedge, edge_a, edge_b, flag, pos, ecomp, node_img, obs_node, obs_key);
+    INSFM_HIP(hipMemcpyAsync(host, pos + nq - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(hipMemcpyAsync(host + 1, flag + nq - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    INSFM_HIP(settle(s));
     const int nobs = host[0] + host[1];
-    k_track_nodes<<<grid(nt), kT, 0, s>>>(nt, cstart, pos, nobs, ne, track_nodes);
+    launch(k_track_nodes, nt, s, nt, cstart, pos, nobs, ne, track_nodes);
 
-    b = tmp_bytes;
-    (void)hipcub::DeviceRadixSort::SortPairs(tmp, b, obs_key, skey64, obs_node, snode, nobs, 0, 32 + bits_for(nt), s);
-    k_heads<unsigned long long><<<grid(nobs), kT, 0, s>>>(nobs, skey64, head);
-    b = tmp_bytes;
-    (void)hipcub::DeviceScan::InclusiveSum(tmp, b, head, incl, nobs, s);
-    k_starts<<<grid(nobs), kT, 0, s>>>(nobs, head, incl, gstart);
-    (void)hipMemcpyAsync(host, incl + nobs - 1, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return INSFM_BA_EHIP;
-    const int ng = host[0];
+    INSFM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, b = tmp_bytes, obs_key, skey64, obs_node, snode, nobs, 0,
+                                                 32 + bits_for(nt), s));
+    int ng = 0;
+    if (int rc = segment_runs(w, tmp, tmp_bytes, nobs, skey64, head, incl, gstart, &ng)) return rc;
     if (xy_f32)
-        k_rows<float><<<grid(ng), kT, 0, s>>>(ng, gstart, snode, skey64, deg, static_cast<const float*>(node_xy),
-                                              (float)thres_inconsistency, track_bad, row_node, row_track);
+        launch(k_rows<float>, ng, s, ng, gstart, snode, skey64, deg, static_cast<const float*>(node_xy),
+               (float)thres_inconsistency, track_bad, row_node, row_track);
     else
-        k_rows<double><<<grid(ng), kT, 0, s>>>(ng, gstart, snode, skey64, deg, static_cast<const double*>(node_xy),
-                                               thres_inconsistency, track_bad, row_node, row_track);
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return INSFM_BA_EHIP;
+        launch(k_rows<double>, ng, s, ng, gstart, snode, skey64, deg, static_cast<const double*>(node_xy),
+               thres_inconsistency, track_bad, row_node, row_track);
+    INSFM_HIP(settle(s));
     counts[0] = nt;
     counts[1] = ng;
     return INSFM_BA_OK;

@@ -101,8 +101,34 @@ def test_track_of_one_image():
     assert len(check_against_host(ptr, img, 2)[0]) == 3
 
 
+def sorted_keys(ptr, img):
+    """What the radix sort of csrc/covis.hip leaves: (lo << 32) | hi of every ordinal, all ones for a pair of one image."""
+    keys = [(min(a, b) << 32 | max(a, b)) if a != b else 2 ** 64 - 1
+            for s, e in zip(ptr[:-1], ptr[1:]) for i, a in enumerate(img[s:e].tolist()) for b in img[s + i + 1:e].tolist()
+            if e - s > 2]
+    return sorted(keys)
+
+
+def block_edge_scenes():
+    """Ordinal totals of 3, 255, 256 and 257 (3 per 3-row track, 10 per 5-row track): one element, and the 256-thread
+    block edge of the run segmentation.  The last two have 257: in one the run of (3, 9) starts exactly at sorted
+    position 256, in the other it lies on positions 255 | 256."""
+    rng = np.random.default_rng(7)
+    few = lambda n, rows: [rng.integers(0, 7, rows) for _ in range(n)]  # noqa: E731
+    fives = [[0, 1, 2, 3, 4], [0, 1, 2, 3, 9]]
+    scenes = [(3, csr([[4, 2, 7]])), (255, csr(few(85, 3))), (256, csr(few(82, 3) + few(1, 5))),
+              (257, csr([[0, 1, 2]] * 79 + fives)), (257, csr([[0, 1, 2]] * 78 + [[3, 9, 0]] + fives))]
+    starts_at_256, straddles = sorted_keys(*scenes[3][1]), sorted_keys(*scenes[4][1])
+    assert starts_at_256[255] != starts_at_256[256] == (3 << 32 | 9)
+    assert straddles[254] != straddles[255] == straddles[256] == (3 << 32 | 9)
+    return scenes
+
+
 @pytest.mark.parametrize("min_count", [5, 1])
 def test_long_and_ragged_tracks(ragged, min_count):
+    for total, (p, im) in block_edge_scenes():
+        assert len(sorted_keys(p, im)) == covis.host_pairs(p, im, min_count)[4] == total
+        check_against_host(p, im, min_count)
     ptr, img = ragged
     L = np.diff(ptr)
     assert {64, 65, 257, 300} <= set(L.tolist()) and (L == 0).any()

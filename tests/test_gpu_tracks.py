@@ -116,3 +116,22 @@ def test_track_engine_long_chain(capsys):
     p.inliers = np.arange(nf)
     vg.image_pairs[n_img - 1] = p
     _vs_oracle(vg, imgs, capsys)
+    # Single chains at one element and at the 256-thread block edge of the run segmentation: a chain of ne matches is one
+    # component of ne grouped edges and ne + 1 observations.  Every node in an image of its own makes every run of the
+    # (track, image) sort one long; node v in image (v + 1) // 2 makes runs of two, one of them at sorted positions
+    # 255 | 256.  Features within 1.5 px of each other, so no pair exceeds the threshold and the track is kept.
+    for ne in (1, 2, 255, 256, 257):
+        for paired in (False, True):
+            where = [((v + 1) // 2, (v + 1) % 2) if paired else (v, 0) for v in range(ne + 1)]
+            imgs = [Im() for _ in range(where[-1][0] + 1)]
+            for im in imgs:
+                im.features = rng.uniform(0, 1, (2, 2)).astype(np.float32)
+            vg = ViewGraph()
+            for v in range(ne):
+                (i, fi), (j, fj) = where[v], where[v + 1]
+                p = ImagePair(i, j)
+                p.matches = np.array([[fi, fj]], np.uint32)
+                p.inliers = np.arange(1)
+                vg.image_pairs[v] = p
+            full = _vs_oracle(vg, imgs, capsys)
+            assert [len(o) for o in full.values()] == [len(imgs)], (ne, paired)
