@@ -54,6 +54,21 @@ int insfm_pair_inliers(int64_t n_pairs, const int64_t* pair_ptr, int64_t n_match
                        int32_t rays_f32, const int32_t* pair_kind, const double* pair_geom, int32_t* inlier_idx,
                        int32_t* inlier_count, double* score, int32_t* touched, void* stream);
 
+/* Rotation averaging over the pairs' relative rotations (between the pair scoring and the tracks): documented in
+ * insfm_rotavg.h, which declares these too (and defines the options structure). */
+struct insfm_rotavg_options;
+int insfm_rotavg_solve(int64_t n, int64_t n_pairs, const int32_t* pair_i, const int32_t* pair_j,
+                       const double* pair_quat, double* rot, int64_t fixed, const double* fixed_rot,
+                       const struct insfm_rotavg_options* opt, int32_t* info, void* stream);
+int insfm_rotavg_residuals(int64_t n, int64_t n_pairs, const int32_t* pair_i, const int32_t* pair_j,
+                           const double* pair_quat, const double* rot, int64_t fixed, const double* fixed_rot,
+                           double* res, void* stream);
+int insfm_rotavg_update(int64_t n, double* rot, const double* step, void* stream);
+int insfm_rotavg_system(int64_t n, int64_t n_pairs, const int32_t* pair_i, const int32_t* pair_j,
+                        const double* weights, int64_t fixed, double* M, double* inverse, void* stream);
+int insfm_rotavg_pair_errors(int64_t n, int64_t n_pairs, const int32_t* pair_i, const int32_t* pair_j,
+                             const double* pair_quat, const double* world2cam, double* angle_deg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

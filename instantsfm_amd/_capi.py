@@ -55,8 +55,19 @@ class Stats(ctypes.Structure):
                     coarse_used=self.coarse_used)
 
 
+class RotavgOptions(ctypes.Structure):
+    """insfm_rotavg_options (insfm_rotavg.h)."""
+    _fields_ = [
+        ("max_num_l1_iterations", ctypes.c_int32), ("max_num_irls_iterations", ctypes.c_int32),
+        ("l1_step_convergence_threshold", ctypes.c_double), ("irls_step_convergence_threshold", ctypes.c_double),
+        ("irls_loss_parameter_sigma", ctypes.c_double),
+        ("rho", ctypes.c_double), ("alpha", ctypes.c_double), ("absolute_tolerance", ctypes.c_double),
+        ("relative_tolerance", ctypes.c_double),
+    ]
+
+
 # exported symbols (every one declared in include/*.h): the product ABI (insfm_ba.h, insfm_gp.h, insfm_passes.h,
-# insfm_tracks.h, insfm_covis.h) and the introspection / prototype entry points of insfm_ba_debug.h
+# insfm_tracks.h, insfm_covis.h, insfm_pairs.h, insfm_rotavg.h) and the introspection / prototype entry points of insfm_ba_debug.h
 PUBLIC_SYMBOLS = ("insfm_build_info", "insfm_ba_default_desc", "insfm_ba_create", "insfm_ba_step", "insfm_ba_cost",
                   "insfm_ba_reset", "insfm_ba_destroy", "insfm_ba_last_error", "insfm_ba_exchange_count",
                   "insfm_ba_set_exchange", "insfm_ba_set_timing", "insfm_ba_release_cache",
@@ -65,7 +76,9 @@ PUBLIC_SYMBOLS = ("insfm_build_info", "insfm_ba_default_desc", "insfm_ba_create"
                   "insfm_gp_default_desc", "insfm_gp_create", "insfm_gp_step", "insfm_gp_cost",
                   "insfm_undistort", "insfm_filter_reproj_normalized", "insfm_filter_angle", "insfm_filter_tri_angle",
                   "insfm_filter_reproj_pixel", "insfm_reproj_candidates",
-                  "insfm_tracks_establish", "insfm_covis_pairs", "insfm_pair_inliers")
+                  "insfm_tracks_establish", "insfm_covis_pairs", "insfm_pair_inliers",
+                  "insfm_rotavg_solve", "insfm_rotavg_residuals", "insfm_rotavg_update", "insfm_rotavg_system",
+                  "insfm_rotavg_pair_errors")
 DEBUG_SYMBOLS = ("insfm_ba_debug_linearize", "insfm_ba_debug_solve", "insfm_ba_debug_get", "insfm_ba_nnzb",
                  "insfm_ba_debug_time_kernel", "insfm_ba_debug_clusters", "insfm_ba_debug_spd_inverse",
                  "insfm_ba_debug_time_cgp", "insfm_ba_debug_stamps",
@@ -199,6 +212,14 @@ def load(path=None):
     L.insfm_covis_pairs.restype = ctypes.c_int
     L.insfm_pair_inliers.argtypes = [i64, vp, i64, vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.insfm_pair_inliers.restype = ctypes.c_int
+    L.insfm_rotavg_solve.argtypes = [i64, i64, vp, vp, vp, vp, i64, vp, ctypes.POINTER(RotavgOptions), ip, vp]
+    L.insfm_rotavg_residuals.argtypes = [i64, i64, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.insfm_rotavg_update.argtypes = [i64, vp, vp, vp]
+    L.insfm_rotavg_system.argtypes = [i64, i64, vp, vp, vp, i64, vp, vp, vp]
+    L.insfm_rotavg_pair_errors.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp]
+    for fn in ("insfm_rotavg_solve", "insfm_rotavg_residuals", "insfm_rotavg_update", "insfm_rotavg_system",
+               "insfm_rotavg_pair_errors"):
+        getattr(L, fn).restype = ctypes.c_int
     for fn in ("insfm_tracks_establish", "insfm_undistort", "insfm_filter_reproj_normalized", "insfm_filter_angle", "insfm_filter_tri_angle",
                "insfm_filter_reproj_pixel", "insfm_reproj_candidates",
            "insfm_tracks_establish"):

@@ -13,7 +13,7 @@ import sysconfig
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, "csrc", n) for n in ("ba_kernels.hip", "passes.hip", "tracks.hip", "covis.hip",
-                                                   "pair_inliers.hip")]
+                                                   "pair_inliers.hip", "rotavg.hip")]
 HEADERS = [*sorted(glob.glob(os.path.join(HERE, "csrc", "*.h"))), *sorted(glob.glob(os.path.join(REPO, "include", "*.h")))]
 OBJDIR = os.path.join(REPO, "build", "obj")
 OUT = os.path.join(HERE, "_lib", "libinsfm_ba.so")

@@ -22,6 +22,14 @@ pose, on the GPU), FilterInlierNum, FilterInlierRatio and ``view_graph.keep_larg
 supplies each pair's relative pose (``rotation`` xyzw, ``translation``), plus ``F`` / ``H`` where the pair's config
 needs them.  It adds ``timings['pair_inliers_s']`` and a first trace entry ``('pair_inliers', valid pairs, total
 inliers, None)``.  Relative pose estimation itself stays out of scope, and so does its ``skip_*`` switch.
+
+``rotation_averaging=True`` makes the mapper produce the images' rotations itself, as reference lines :59-78 do:
+RotationEstimator.EstimateRotations (on the GPU), FilterRotations with ``max_rotation_error`` and
+``view_graph.keep_largest_connected_component``, then all three once more.  The caller supplies each pair's
+``rotation`` and ``inliers`` (or ``pair_inliers=True``) and the images' ``is_registered`` flags; the images need no
+rotations.  It adds ``timings['rotation_averaging_s']`` and a trace entry ``('rotation_averaging', registered images,
+valid pairs, None)``.  Where the reference calls ``exit()`` the mapper raises RuntimeError.  ``skip_rotation_averaging``
+must still be set: the keyword, not the switch, selects the stage.
 """
 import time
 
@@ -31,7 +39,8 @@ from ..processors.image_pair_inliers import ImagePairInliersCount
 from ..processors.image_undistortion import UndistortImages
 from ..processors.reconstruction_normalizer import NormalizeReconstruction
 from ..processors.reconstruction_pruning import PruneWeaklyConnectedImages
-from ..processors.relpose_filter import FilterInlierNum, FilterInlierRatio
+from ..processors.relpose_filter import FilterInlierNum, FilterInlierRatio, FilterRotations
+from ..processors.rotation_averaging import RotationEstimator
 from ..processors.track_establishment import TrackEngine
 from ..processors.track_filter import (FilterTracksByAngle, FilterTracksByReprojectionNormalized,
                                        FilterTracksTriangulationAngle, collect_tracks)
@@ -53,10 +62,10 @@ def _banner(msg):
 
 
 def SolveGlobalMapper(view_graph, cameras, images, config, depths=None, visualizer=None, device="cuda:0",
-                      timings=None, progress=False, pair_inliers=False):
+                      timings=None, progress=False, pair_inliers=False, rotation_averaging=False):
     """global_mapper.py:21-156 from track establishment on.  Returns (cameras, images, tracks) like the reference.
     ``pair_inliers=True`` first scores every valid pair's matches and thins the view graph (:46-56 without
-    EstimateRelativePose)."""
+    EstimateRelativePose); ``rotation_averaging=True`` then estimates the images' rotations from the pairs' (:59-78)."""
     for key in OUT_OF_SCOPE_STAGES:
         if not config.OPTIONS[key]:
             raise NotImplementedError(f"{key}=False: that stage (global_mapper.py:22-78) is outside this "
@@ -80,6 +89,23 @@ def SolveGlobalMapper(view_graph, cameras, images, config, depths=None, visualiz
         trace.append(('pair_inliers', len(valid), int(sum(len(pair.inliers) for pair in valid)), None))
         T['pair_inliers_s'] = time.time() - start_time
         print('Image pair inlier scoring took: ', T['pair_inliers_s'])
+
+    if rotation_averaging:                                                                      # :59-78
+        _banner('Running rotation averaging ...')
+        start_time = time.time()
+        ra_engine = RotationEstimator(device=device)
+        for _ in range(2):
+            ra_engine.EstimateRotations(view_graph, images, config.ROTATION_ESTIMATOR_OPTIONS,
+                                        config.L1_SOLVER_OPTIONS)
+            FilterRotations(view_graph, images, config.INLIER_THRESHOLD_OPTIONS['max_rotation_error'], device=device)
+            if not view_graph.keep_largest_connected_component(images):
+                raise RuntimeError('Failed to keep the largest connected component.')
+        num_img = sum([1 for img in images if img.is_registered])
+        print(num_img, '/', len(images), 'images are within the connected component.')
+        trace.append(('rotation_averaging', num_img,
+                      sum(1 for pair in view_graph.image_pairs.values() if pair.is_valid), None))
+        T['rotation_averaging_s'] = time.time() - start_time
+        print('Rotation averaging took: ', T['rotation_averaging_s'])
 
     if not config.OPTIONS['skip_track_establishment']:                                          # :80-91
         _banner('Running track establishment ...')

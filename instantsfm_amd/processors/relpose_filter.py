@@ -1,10 +1,12 @@
-"""FilterInlierNum / FilterInlierRatio -- drop-ins for ``instantsfm/processors/relpose_filter.py`` (reference :25-43),
-the view-graph filters after ImagePairInliersCount.  Host code: one pass collects the valid pairs' inlier and match
-counts, the comparison is vectorised, the printed lines are the reference's.  ``FilterRotations`` (:5-23) belongs to
-rotation averaging and is not part of this build.
+"""FilterRotations / FilterInlierNum / FilterInlierRatio -- drop-ins for ``instantsfm/processors/relpose_filter.py``
+(reference :5-43), the view-graph filters after rotation averaging and after ImagePairInliersCount.  The inlier filters
+are host code: one pass collects the valid pairs' inlier and match counts, the comparison is vectorised.
+``FilterRotations`` computes every pair's angle in one ``insfm_rotavg_pair_errors`` call (csrc/rotavg.hip), or in numpy
+for ``device`` ``"cpu"`` / ``None``.  The printed lines are the reference's.
 """
 import numpy as np
 
+from .. import rotavg as RA
 from ..scene.defs import ViewGraph
 
 
@@ -19,6 +21,22 @@ def _invalidate(pairs, drop):
     for k in np.flatnonzero(drop).tolist():
         pairs[k].is_valid = False
     return int(np.count_nonzero(drop))
+
+
+def FilterRotations(view_graph: ViewGraph, images, max_angle, device="cuda:0"):
+    """relpose_filter.py:5-23: a valid pair between two registered images whose rotation differs from the images'
+    relative rotation by more than ``max_angle`` degrees becomes invalid (a NaN angle leaves it valid, as the
+    reference's comparison does)."""
+    pairs = [pair for pair in view_graph.image_pairs.values()
+             if pair.is_valid and images[pair.image_id1].is_registered and images[pair.image_id2].is_registered]
+    pair_i = np.array([pair.image_id1 for pair in pairs], dtype=np.int32)
+    pair_j = np.array([pair.image_id2 for pair in pairs], dtype=np.int32)
+    quat = np.array([np.asarray(pair.rotation, dtype=np.float64) for pair in pairs]).reshape(-1, 4)
+    world2cam = np.array([image.world2cam[:3, :3] for image in images], dtype=np.float64).reshape(-1, 3, 3)
+    angle = RA.pair_errors(pair_i, pair_j, quat, world2cam, device=device)
+    with np.errstate(invalid="ignore"):
+        num_invalid = _invalidate(pairs, angle > max_angle)
+    print('Filtered', num_invalid, 'relative rotation with angle >', max_angle, 'degrees')
 
 
 def FilterInlierNum(view_graph: ViewGraph, min_inlier_num):

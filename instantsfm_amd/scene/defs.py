@@ -19,6 +19,8 @@ from typing import List, Optional
 
 import numpy as np
 
+from ..utils.rotation import matrix_to_quat, matrix_to_rotvec, quat_to_matrix
+
 
 class Image:
     """defs.py:8-39."""
@@ -42,6 +44,10 @@ class Image:
     def center(self):
         return self.world2cam[:3, :3].T @ -self.world2cam[:3, 3]
 
+    def axis_angle(self):
+        """defs.py:38-39: the rotation vector of ``world2cam``'s rotation (angle in [0, pi])."""
+        return matrix_to_rotvec(self.world2cam[:3, :3])
+
 
 class ConfigurationType(Enum):
     """defs.py:41-50 (COLMAP's TwoViewGeometry::ConfigurationType values)."""
@@ -57,7 +63,7 @@ class ConfigurationType(Enum):
 
 
 class ImagePair:
-    """defs.py:52-86 (the fields; relative-pose helpers are off the path)."""
+    """defs.py:52-87 (``rotation`` xyzw and ``translation`` take image 1 to image 2)."""
 
     def __init__(self, image_id1: int = -1, image_id2: int = -1, is_valid: bool = True, weight: float = 0.0,
                  E=None, F=None, H=None, rotation=None, translation=None, inliers=None,
@@ -73,6 +79,18 @@ class ImagePair:
         self.translation = translation if translation is not None else np.zeros(3)
         self.inliers = inliers if inliers is not None else []
         self.config = config
+
+    def set_cam1to2(self, cam1to2: np.ndarray) -> None:
+        """defs.py:80-83."""
+        self.rotation = matrix_to_quat(cam1to2[:3, :3])
+        self.translation = cam1to2[:3, 3]
+
+    def get_cam1to2(self) -> np.ndarray:
+        """defs.py:85-87: the 4x4 of x2 = R x1 + t."""
+        pose = np.eye(4)
+        pose[:3, :3] = quat_to_matrix(self.rotation)
+        pose[:3, 3] = self.translation
+        return pose
 
 
 C_MAX_INT = 2 ** 31 - 1  # defs.py:88

@@ -22,6 +22,10 @@ records:
 * ``pair_inliers_golden.npz`` (``--only inliers``) -- ``ImagePairInliersCount`` (image_pair_inliers.py:7-133) on the
   scenes of tests/pair_scene.py: per valid pair the returned score, whether ``inliers`` was assigned, and the inliers.
 
+* ``rotavg_golden.npz`` (``--only rotavg``) -- ``RotationEstimator.EstimateRotations`` (rotation_averaging.py:177-195) on
+  the 12-image scene of tests/rotavg_scene.py: the pairs, the final rotations and the iteration counts.
+  ``sksparse.cholmod`` (absent here) is answered by a dense scipy Cholesky that also counts its calls.
+
 Only data leaves this script: no reference source is copied into the repository.
 Usage:  python tools/gen_golden.py [--out tests/golden]
 """
@@ -832,11 +836,77 @@ def gen_inliers(out_dir):
           os.path.getsize(path), "bytes")
 
 
+def gen_rotavg(out_dir):
+    """RotationEstimator.EstimateRotations on tests/rotavg_scene.py's ``ring12`` in the reference's own classes, with
+    the default options.  ``sksparse.cholmod.cholesky`` is a dense ``scipy.linalg.cho_factor`` whose factorisations and
+    solves are logged, and ``L1Solver.solve`` logs its calls; the iteration counts are read off that log: one solve
+    per ADMM iteration, one factorisation per IRLS iteration after the one SolveIRLS starts with."""
+    import contextlib
+    import io
+
+    from scipy.linalg import cho_factor, cho_solve
+    log = []
+
+    class Factor:
+        def __init__(self, A):
+            log.append("factor")
+            self.c = cho_factor(np.asarray(A.todense()))
+
+        def __call__(self, b):
+            log.append("solve")
+            return cho_solve(self.c, np.asarray(b))
+    sk, ch = types.ModuleType("sksparse"), types.ModuleType("sksparse.cholmod")
+    sk.cholmod, ch.cholesky = ch, Factor
+    sys.modules["sksparse"], sys.modules["sksparse.cholmod"] = sk, ch
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import rotavg_scene as RS
+    from instantsfm.processors import rotation_averaging as RAV
+    from instantsfm.scene import defs as ref_defs
+    from instantsfm.utils import l1_solver
+    inner = l1_solver.L1Solver.solve
+
+    def logged(self, rhs, options):
+        log.append("l1")
+        return inner(self, rhs, options)
+    l1_solver.L1Solver.solve = logged
+    vg0, images0, _ = RS.scene("ring12")
+    images = [ref_defs.Image(id=im.id, is_registered=im.is_registered) for im in images0]
+    vg = ref_defs.ViewGraph()
+    for key, p in vg0.image_pairs.items():
+        vg.image_pairs[key] = ref_defs.ImagePair(image_id1=p.image_id1, image_id2=p.image_id2, is_valid=p.is_valid,
+                                                 rotation=np.array(p.rotation), translation=np.array(p.translation),
+                                                 inliers=np.array(p.inliers))
+    with contextlib.redirect_stdout(io.StringIO()):
+        ok = RAV.RotationEstimator().EstimateRotations(vg, images, dict(RS.RO), dict(RS.LO))
+    l1_solver.L1Solver.solve = inner
+    assert ok
+    admm, k = [], 0
+    while k < len(log):
+        if log[k] == "l1":
+            count = 0
+            while k + 1 < len(log) and log[k + 1] == "solve":
+                count, k = count + 1, k + 1
+            admm.append(count)
+        k += 1
+    last_l1 = max(i for i, e in enumerate(log) if e == "l1")
+    irls = log[last_l1:].count("factor") - 1
+    pairs = list(vg0.image_pairs.values())
+    path = os.path.join(out_dir, "rotavg_golden.npz")
+    np.savez_compressed(path, pair_i=np.array([p.image_id1 for p in pairs], np.int32),
+                        pair_j=np.array([p.image_id2 for p in pairs], np.int32),
+                        quat=np.array([p.rotation for p in pairs]),
+                        n_inliers=np.array([len(p.inliers) for p in pairs], np.int32),
+                        rotations=np.array([im.world2cam[:3, :3] for im in images]),
+                        admm=np.array(admm, np.int32), irls=np.array(irls, np.int32))
+    print("rotavg_golden.npz", len(pairs), "pairs, ADMM", admm, "IRLS", irls, os.path.getsize(path), "bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
     ap.add_argument("--only", choices=("projection", "packing", "gp", "passes", "retri", "tracks", "depth", "pruning",
-                                       "inliers"),
+                                       "inliers", "rotavg"),
                     default=None)
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
@@ -862,6 +932,8 @@ def main():
             gen_pruning(args.out)
         if args.only in (None, "inliers"):
             gen_inliers(args.out)
+        if args.only in (None, "rotavg"):
+            gen_rotavg(args.out)
 
 
 if __name__ == "__main__":
