@@ -320,6 +320,7 @@ typedef struct {
     double stats[9];  /* trials, pcg last, pcg total, damping factor, damping, failed, rejects, coarse used,
                          A-DEF2 solves of the step repeated with the additive correction (breakdown) */
     int adef2_fallbacks;  /* (since the last ora_step) */
+    double quality;       /* gain ratio of the last trial of the last step (ora_quality) */
 } ora_t;
 
 static double det_sum_order(const double* v, size_t n, int reverse) {
@@ -1428,6 +1429,7 @@ int ora_step(ora_t* h, double* cams, double* pts, double* loss_out) {
         double loss_new = ora_cost(h, h->cams_new, h->pts_new, NULL);
         double denom = model_decrease(h, cams, pts, h->optimize_poses ? h->x : NULL);
         double quality = (last - loss_new) / denom;
+        h->quality = quality;
         /* pypose TrustRegion.update */
         double radius = 1.0 / h->damping;
         if (quality > h->high) { radius = h->up * radius; h->down = h->down0; }
@@ -1702,6 +1704,7 @@ int ora_gp_step(ora_t* h, double* cams, double* pts, double* scales, double* los
         const double loss_new = ora_gp_cost(h, h->cams_new, h->pts_new, h->gp_scales_new, NULL);
         const double denom = gp_model_decrease(h);
         const double quality = (last - loss_new) / denom;
+        h->quality = quality;
         double radius = 1.0 / h->damping;
         if (quality > h->high) { radius = h->up * radius; h->down = h->down0; }
         else if (quality > h->low) { h->down = h->down0; }
@@ -1730,6 +1733,8 @@ void ora_gp_get_ds(const ora_t* h, double* out) { memcpy(out, h->gp_ds, sizeof(d
 
 void ora_stats(const ora_t* h, double* out) { memcpy(out, h->stats, sizeof(h->stats)); }
 double ora_damping(const ora_t* h) { return h->damping; }
+/* gain ratio (loss decrease over model decrease) of the last trial of the last step */
+double ora_quality(const ora_t* h) { return h->quality; }
 
 /* copy internal buffers out (parity tests) */
 int ora_get(const ora_t* h, int which, double* out) {

@@ -59,6 +59,8 @@ def _bind(L):
         L.ora_nnzb.argtypes = [ctypes.c_void_p]
         L.ora_pattern.argtypes = [ctypes.c_void_p, _ip, _ip]
         L.ora_stats.argtypes = [ctypes.c_void_p, _dp]
+        L.ora_quality.restype = ctypes.c_double
+        L.ora_quality.argtypes = [ctypes.c_void_p]
         L.ora_eval.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
         L.ora_retract_pose.argtypes = [_dp, _dp, _dp]
         L.ora_n_intr.argtypes = [ctypes.c_int]
@@ -170,6 +172,10 @@ class OracleBA:
         self.L.ora_stats(self.h, _d(s))
         return dict(trials=int(s[0]), pcg_iters=int(s[1]), pcg_total=int(s[2]), damp_factor=s[3],
                     damping=s[4], failed=int(s[5]), rejects=int(s[6]), coarse_used=int(s[7]), adef2_fallbacks=int(s[8]))
+
+    def quality(self):
+        """gain ratio (loss decrease over model decrease) of the last trial of the last step"""
+        return self.L.ora_quality(self.h)
 
     def cost(self, cams, pts):
         sq = ctypes.c_double()
