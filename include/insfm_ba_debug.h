@@ -20,7 +20,11 @@ int insfm_ba_debug_linearize(insfm_ba* h, const double* cam_params, const double
 int insfm_ba_debug_solve(insfm_ba* h, double f);
 /* Copy an internal buffer to HOST memory: 0 the camera-point records Y[N,3,D] (Y_o = W_o R_p^-T, R_p the Cholesky
  * factor of point p's block damped for the first trial: S = U - sum Y Y^T; column-major blocks) 1 V[P,6] 2 g_p[P,3] 3 U[C,D,D] 4 g_c[C,D] 5 S(scaled after a
- * solve)[nnzb,D,D] 6 b[C,D] 7 dc[C,D] 8 dp[P,3].  Returns the number of doubles copied or a negative code. */
+ * solve)[nnzb,D,D] 6 b[C,D] 7 dc[C,D] 8 dp[P,3].  Two-level handles (0 doubles otherwise), m = clusters x (D + 1):
+ * 9 u 10 w 11 the restriction's row partials [C,D+1] 12 / 13 E^-1 of coarse-inverse slot 0 / 1 [m,m] 14 the row
+ * partials [r.u | w.u] 15 r 16 / 17 E of slot 0 / 1 padded to whole 32-blocks [ld,ld] (E^-1 once the slot's inversion
+ * has run) 18 the scaled coarse basis Z~ [C,D,D+1] of the last solve.  Returns the number of doubles copied or a
+ * negative code. */
 int64_t insfm_ba_debug_get(insfm_ba* h, int32_t which, double* host_out);
 /* Device time per launch (us, hipEvents on the library stream) of `reps` back-to-back launches of one kernel on the
  * data of the last solve: which = 0 k_cg_iter (one block-Jacobi CG iteration), 1 k_schur, 2 one two-level CG

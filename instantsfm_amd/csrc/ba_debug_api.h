@@ -356,6 +356,8 @@ int64_t insfm_ba_debug_get(insfm_ba* h, int32_t which, double* host) {
         case 15: src = h->cg.r[0]; n = C * D; break;
         // 16/17 E slot 0/1 padded to whole blocks [ldE][ldE] (E^-1 once the slot's inversion has run)
         case 16: case 17: src = h->Ebuf[which - 16]; n = h->tlon ? (size_t)h->tl.ldE * h->tl.ldE : 0; break;
+        // 18 the scaled coarse basis Z~ [C][D][MC] of the last two-level solve
+        case 18: src = h->tl.Zt; n = h->tlon ? C * D * (D + 1) : 0; break;
         default: return INSFM_BA_EINVAL;
     }
     if (int rc0 = side_flush(h)) return rc0;

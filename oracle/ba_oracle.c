@@ -302,6 +302,9 @@ typedef struct {
     int *csize;                  /* cameras per cluster */
     double* lin_cams;            /* copy of the linearization point (coarse basis) */
     double* prev_einv;           /* coarse inverse of the previous solve (lag rule: see ora_pcg) */
+    /* copies of the last two-level solve's coarse operators for ora_get (tests/test_ba_precond_reference.py): Z~
+     * [C][D][MC], E [m][m] before equilibration, the E^-1 this solve built and the E^-1 its CG ran with */
+    double *exp_zt, *exp_e, *exp_einv_built, *exp_einv_used;
     int kind;                    /* 0 bundle adjustment, 1 global positioning (ora_gp_*) */
     int u_predamped;             /* U already holds the damped camera blocks (global positioning) */
     /* global positioning (TorchGP.Optimize): per obs ray t, factor f, scale-free flag, linearization terms */
@@ -646,7 +649,8 @@ void ora_destroy(ora_t* h) {
     void* ptrs[] = {h->uv, h->pp, h->cam, h->pt, h->pt_ptr, h->cam_ptr, h->cam_obs, h->row_ptr, h->col, h->lo_ptr,
                     h->lo_col, h->lo_blk, h->W, h->V, h->gp, h->U, h->gc, h->Vinv, h->y, h->S, h->b, h->Minv, h->x,
                     h->r, h->z, h->p, h->q, h->dp, h->cams_new, h->pts_new, h->partial,
-                    h->clab, h->csize, h->lin_cams, h->prev_einv, h->gp_t, h->gp_f, h->gp_beta, h->gp_a,
+                    h->clab, h->csize, h->lin_cams, h->prev_einv, h->exp_zt, h->exp_e, h->exp_einv_built,
+                    h->exp_einv_used, h->gp_t, h->gp_f, h->gp_beta, h->gp_a,
                     h->gp_r, h->gp_hss, h->gp_gs, h->gp_ds, h->gp_hx, h->gp_hc, h->gp_gx, h->gp_gc,
                     h->gp_scales_new, h->gp_sfree, h->gp_ref};
     for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i) free(ptrs[i]);
@@ -1020,6 +1024,7 @@ static int ora_coarse_setup(ora_t* h, const double* Lfac, double* Zt, double* Ei
     }
     for (int k = 0; k < m; ++k)
         if (E[(size_t)k * m + k] == 0.0) E[(size_t)k * m + k] = 1.0;
+    if (h->exp_e) memcpy(h->exp_e, E, sizeof(double) * (size_t)m * m);
     /* symmetric equilibration d = 1 / sqrt(diag E) (the GPU's k_gj_equil; NaN for a non-positive diagonal, which
      * fails the first pivot test), then E^-1 = diag(d) (diag(d) E diag(d))^-1 diag(d) */
     double* dq = (double*)malloc(sizeof(double) * (size_t)m);
@@ -1169,7 +1174,15 @@ int ora_pcg(ora_t* h, double* xout) {
          * GPU factorizes E_k on a side stream while that CG runs; later solves at the same linearization (rejected LM
          * trials, whose damping can jump by 16x per retry) and the very first solve use their own E.  Any SPD E^-1
          * keeps M~ SPD, so the lag only changes the iteration count (a few percent). */
+        if (!h->exp_zt) {
+            h->exp_zt = (double*)malloc(sizeof(double) * (size_t)C * D * MC);
+            h->exp_e = (double*)malloc(sizeof(double) * (size_t)m * m);
+            h->exp_einv_built = (double*)malloc(sizeof(double) * (size_t)m * m);
+            h->exp_einv_used = (double*)malloc(sizeof(double) * (size_t)m * m);
+        }
         int okc = ora_coarse_setup(h, Lfac, Zt, Einv);
+        memcpy(h->exp_zt, Zt, sizeof(double) * (size_t)C * D * MC);
+        memcpy(h->exp_einv_built, Einv, sizeof(double) * (size_t)m * m);
         if (!h->prev_einv) h->prev_einv = (double*)malloc(sizeof(double) * (size_t)m * m);
         if (h->have_prev && h->fresh_lin) {
             for (size_t e = 0; e < (size_t)m * m; ++e) { double tmp = Einv[e]; Einv[e] = h->prev_einv[e]; h->prev_einv[e] = tmp; }
@@ -1180,6 +1193,7 @@ int ora_pcg(ora_t* h, double* xout) {
             h->have_prev = 1;
         }
         h->fresh_lin = 0;
+        memcpy(h->exp_einv_used, Einv, sizeof(double) * (size_t)m * m);
         if (!okc) twolev = 0;
     }
     /* A-DEF2 breakdown (the recurrence's denominator <= 0: possible under the lag rule, whose E^-1 is the previous
@@ -1749,6 +1763,15 @@ int ora_get(const ora_t* h, int which, double* out) {
         case 6: memcpy(out, h->b, sizeof(double) * C * D); return 0;
         case 7: memcpy(out, h->x, sizeof(double) * C * D); return 0;
         case 8: memcpy(out, h->dp, sizeof(double) * P * 3); return 0;
+        /* the last two-level solve's coarse operators: 9 Z~ [C][D][D+1], 10 E [m][m] before equilibration (m = nclust
+         * (D + 1)), 11 the E^-1 that solve built, 12 the E^-1 its CG ran with (the previous solve's under the lag rule) */
+        case 9: case 10: case 11: case 12: {
+            const size_t m = (size_t)h->nclust * (D + 1);
+            const double* src[4] = {h->exp_zt, h->exp_e, h->exp_einv_built, h->exp_einv_used};
+            if (!src[which - 9]) return -1;
+            memcpy(out, src[which - 9], sizeof(double) * (which == 9 ? C * D * (D + 1) : m * m));
+            return 0;
+        }
         default: return -1;
     }
 }

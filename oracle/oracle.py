@@ -22,6 +22,9 @@ _ip = ctypes.POINTER(ctypes.c_int)
 
 # buffer ids for ora_get
 W, V, GP, U, GC, S, B, DC, DP = range(9)
+# the last two-level solve's coarse operators: Z~ [C,D,D+1], E [m,m] before equilibration, the E^-1 that solve built and
+# the E^-1 its CG ran with (the previous solve's under the lag rule)
+ZT, E, EINV_BUILT, EINV_USED = range(9, 13)
 
 
 def build(quiet=True):
@@ -213,8 +216,12 @@ class OracleBA:
         shapes = {W: (self.N, self.D, 3), V: (self.P, 6), GP: (self.P, 3), U: (self.C, self.D, self.D),
                   GC: (self.C, self.D), S: (self.nnzb(), self.D, self.D), B: (self.C, self.D),
                   DC: (self.C, self.D), DP: (self.P, 3)}
+        if which >= ZT:
+            m = self.clusters()[1] * (self.D + 1)
+            shapes = {ZT: (self.C, self.D, self.D + 1), E: (m, m), EINV_BUILT: (m, m), EINV_USED: (m, m)}
         out = np.zeros(shapes[which])
-        self.L.ora_get(self.h, which, _d(out))
+        if self.L.ora_get(self.h, which, _d(out)) != 0:
+            raise ValueError(f"ora_get({which}): nothing to hand out")
         return out
 
 

@@ -91,25 +91,30 @@ def problem(name, model):
     return _cache["problem", name, model]
 
 
-def observed(name, model):
-    """ba_solve_reference.observe at the scene's initial parameters"""
-    if ("obs", name, model) not in _cache:
+def observed(name, model, point=None):
+    """ba_solve_reference.observe at the scene's initial parameters, or at `point` = (tag, cams, pts): another
+    linearization point, cached under its tag"""
+    key = ("obs", name, model, None if point is None else point[0])
+    if key not in _cache:
         p = problem(name, model)
+        cams, pts = (p.cams_init, p.points_init) if point is None else point[1:]
         # the planted track's projections cancel 30 against 30 down to a depth of 0.025: those rows come from mpmath
         mask = (p.pt_idx == N_TRACKS) if name == "clamps" else None
-        _cache["obs", name, model] = B.observe(p, p.cams_init, p.points_init, settings(name, model)["huber_delta"], mask)
-    return _cache["obs", name, model]
+        _cache[key] = B.observe(p, cams, pts, settings(name, model)["huber_delta"], mask)
+    return _cache[key]
 
 
-def system(name, model, f, mutate=None):
-    """the reduced reference system for damping factor f, cached per process and shared by det, precond and the tests:
-    the last KEEP_SYSTEMS of them, so callers walk the cases scene by scene, model by model"""
-    key = ("sys", name, model, float(f), mutate)
+def system(name, model, f, mutate=None, point=None):
+    """the reduced reference system for damping factor f at the initial parameters (or at `point`, as observed()),
+    cached per process and shared by det, precond and the tests: the last KEEP_SYSTEMS of them, so callers walk the
+    cases scene by scene, model by model"""
+    key = ("sys", name, model, float(f), mutate, None if point is None else point[0])
     if key in _cache:
         _cache[key] = _cache.pop(key)                  # most recently used last
     else:
         kw = settings(name, model)
-        _cache[key] = B.reduce(observed(name, model), f, clamp_min=kw["clamp_min"], clamp_max=kw["clamp_max"], mutate=mutate)
+        _cache[key] = B.reduce(observed(name, model, point), f, clamp_min=kw["clamp_min"], clamp_max=kw["clamp_max"],
+                               mutate=mutate)
         held = [k for k in _cache if k[0] == "sys"]
         for k in held[:-KEEP_SYSTEMS]:                 # a dense S and its |terms| are 160 MB at D = 16: keep a few
             del _cache[k]
